@@ -6,13 +6,18 @@ resident in HBM (BASELINE.json configs[1], the configuration the metric is quote
 rank transforms its own 64-image batch shard (weak scaling, no data-path collective: batch elements are
 independent); the only collectives are the barrier and the max-over-ranks of the wall time.
 
-Output: ONE JSON line on rank 0 with the whole-job throughput in Msamples/s, plus
+Output: ONE JSON line on rank 0 with the whole-job throughput in Msamples/s and ms_per_step.  A plain run does only that: set up,
+warm up, time the --steps steps, write the last step's outputs (--dump-outputs DIR), print the line.  With --full the line also holds
   "roofline"     achieved algorithmic GB/s of the dominant kernel (the level-1 analysis kernel), measured
                  live with HIP events on the launch stream inside the timed region, against 8 TB/s HBM peak;
+  "whole_call"   (always there: compulsory bytes and fraction of the peak) + per-level kernel times, the rotating-outputs and
+                 collector-on figures (loops of their own);
+  "secondary"    the other BASELINE configurations (headline workload, N = 1);
   "cpu_baseline" the reference's CPU op sequence (oracle/torch_cpu_port.py) timed on this host's cores
-                 (N = 1 only).
+                 (N = 1 only);
+  "config4_shard" N > 1: config 4's per-GPU shard on every rank and the gather of its coefficients.
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps 50 --warmup 5
 """
 from __future__ import annotations
@@ -144,6 +149,35 @@ def _flatten(coeffs):
         else:
             out.extend((f"{i}_{j}", v) for j, v in enumerate(c))
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out, path, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what a caller of the timed path received from its last step, one ``path/<name>.npy`` per returned tensor
+    (``out`` for a single tensor, ``out_<position>`` in a coefficient list or gradient tuple), float64 kept, every other dtype
+    written as float32.  Over ``budget`` bytes in all, every array is cut to the same fraction of its elements, at positions drawn
+    from a fixed seed (the same positions in every run with the same arguments), and written as the 1-D array of those elements
+    in ascending flat order.  Returns {name: shape written}."""
+    import numpy as np
+
+    named = [("out", out)] if isinstance(out, torch.Tensor) else [("out_" + n, t) for n, t in _flatten(out)]
+    named = [(n, t.detach()) for n, t in named]
+    wdtype = [torch.float64 if t.dtype == torch.float64 else torch.float32 for _, t in named]
+    total = sum(t.numel() * torch.empty(0, dtype=d).element_size() for (_, t), d in zip(named, wdtype))
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for j, ((name, t), d) in enumerate(zip(named, wdtype)):
+        if total > budget:
+            k = max(1, t.numel() * budget // total)
+            flat = torch.randint(t.numel(), (k,), generator=torch.Generator().manual_seed(20240 + j)).sort().values
+            # (multi-dimensional indices: the coefficient tensors are strided views of level buffers, no dense copy of them)
+            t = t[torch.unravel_index(flat.to(t.device), t.shape)]
+        a = t.to(d).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def cpu_baseline(fn, shape, wavelet, level, mode, dtype):
@@ -475,12 +509,21 @@ def main():
                          "milliseconds of load (measured: 0.172 ms/step over the first 50 steps vs 0.157 steady)")
     ap.add_argument("--workload", default="wavedec2_db4_L3_64x1024x1024_f32", choices=sorted(WORKLOADS))
     ap.add_argument("--buffers", type=int, default=3, help="distinct input buffers rotated to defeat the 256 MiB Infinity Cache")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short list of other workloads timed after the headline (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run everything else the line can report: roofline and per-kernel legs, rotating-output "
+                         "and collector-on loops, secondary workloads, CPU baseline, N > 1 shard leg (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, float64 for f64 workloads; a fixed, seeded "
+                         "sample of every array when all of it exceeds 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short list of other workloads timed after the headline "
+                                                                "(N = 1) and the shard leg (N > 1)")
     ap.add_argument("--gather", action="store_true",
                     help="N > 1: also time (outside the timed region) the all-gather that would replicate the coefficients on "
                          "every rank; opt-in because it cannot be exercised on the one-GPU development boxes")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -594,8 +637,9 @@ def main():
     sync()
 
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(i)
+    last = step(args.steps - 1)  # (only the last result is kept: every other step's output block is freed as before)
     sync()
     if distributed:
         dist.barrier()
@@ -603,92 +647,95 @@ def main():
     elapsed = time.perf_counter() - t0
 
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    del last
 
-    # Roofline leg: the same K steps once more with a HIP event pair around every level launch, recorded on
-    # the launch stream.  It is a separate pass because hipEventRecord inserts a barrier packet into the
-    # queue: inside the headline region it cost 35 % of the throughput (0.238 vs 0.176 ms/step measured).
-    _engine.level_events = []
-    for i in range(args.steps):
-        step(i)
-    sync()
-    events, _engine.level_events = _engine.level_events, None
-
-    # Dominant-kernel leg: the first launch of a call (the multi-level kernel where it serves the call), 10 batches of 20
-    # launches back to back on the launch stream, one HIP event pair per batch (an event pair around every launch adds a
-    # barrier packet on each side of the kernel: +5-8 % on a 100 us kernel).  The count does not depend on --steps; the
-    # median batch is the figure, comparable with the rocprofv3 kernel-trace average under profiles/.
-    lvl1_b2b_ms = lvl1_b2b_min = None
-    lbufs = bufs  # inputs of the dominant-launch leg
-    fused_levels = 1
-    first_kid = events[0][1] if events else -1
-    launch = None
-    call_is_launch = False
-    if is_rec and not is_bwd and events and len({e[2] for e in events}) == 1:
-        # the whole reconstruction is ONE launch (the streaming / small-plane multi-level kernels): the call is the launch
-        first_kid = events[-1][1]
-        fused_levels = level
-        launch = lambda b: fn(b, wavelet)  # noqa: E731
-        call_is_launch = True
-    elif fn_name in ("wavedec2", "fswavedec2", "wavedec3", "wavedec", "wavedec2_bwd"):
-        taps = ptwt_amd._wavelets.host_taps(wavelet)
-        if is_bwd:
-            lbufs = [b.detach() for b in bufs]  # (the launch leg below calls the engine directly; `step` keeps the leaves)
-        mode_id = _engine.MODE_IDS[mode]
-        if first_kid in (_engine.KID_PYRAMID, _engine.KID_SMALL):
-            fused_levels = len(_engine.ENGINE.analysis_pyramid(lbufs[0], taps[0], taps[1], mode_id, level))
-            launch = lambda b: _engine.ENGINE.analysis_pyramid(b, taps[0], taps[1], mode_id, level)  # noqa: E731
-        elif first_kid == _engine.KID_PAIR:
-            fused_levels = 2
-            launch = lambda b: _engine.ENGINE.analysis_pair(b, taps[0], taps[1], mode_id)  # noqa: E731
-        elif first_kid == _engine.KID_LONG:
-            fused_levels = len(_engine.ENGINE.analysis_tail(lbufs[0], taps[0], taps[1], mode_id, level))
-            launch = lambda b: _engine.ENGINE.analysis_tail(b, taps[0], taps[1], mode_id, level)  # noqa: E731
-        else:
-            launch = lambda b: _engine.ENGINE.analysis(b, taps[0], taps[1], mode_id)  # noqa: E731
-    if launch is not None:
-        for i in range(5):
-            launch(lbufs[i % len(lbufs)])
+    if args.full:
+        # Roofline leg: the same K steps once more with a HIP event pair around every level launch, recorded on
+        # the launch stream.  It is a separate pass because hipEventRecord inserts a barrier packet into the
+        # queue: inside the headline region it cost 35 % of the throughput (0.238 vs 0.176 ms/step measured).
+        _engine.level_events = []
+        for i in range(args.steps):
+            step(i)
         sync()
-        batches = []
-        for _b in range(10):
-            e0, e1 = new_event(), new_event()
-            e0.record()
-            for i in range(20):
+        events, _engine.level_events = _engine.level_events, None
+
+        # Dominant-kernel leg: the first launch of a call (the multi-level kernel where it serves the call), 10 batches of 20
+        # launches back to back on the launch stream, one HIP event pair per batch (an event pair around every launch adds a
+        # barrier packet on each side of the kernel: +5-8 % on a 100 us kernel).  The count does not depend on --steps; the
+        # median batch is the figure, comparable with the rocprofv3 kernel-trace average under profiles/.
+        lvl1_b2b_ms = lvl1_b2b_min = None
+        lbufs = bufs  # inputs of the dominant-launch leg
+        fused_levels = 1
+        first_kid = events[0][1] if events else -1
+        launch = None
+        call_is_launch = False
+        if is_rec and not is_bwd and events and len({e[2] for e in events}) == 1:
+            # the whole reconstruction is ONE launch (the streaming / small-plane multi-level kernels): the call is the launch
+            first_kid = events[-1][1]
+            fused_levels = level
+            launch = lambda b: fn(b, wavelet)  # noqa: E731
+            call_is_launch = True
+        elif fn_name in ("wavedec2", "fswavedec2", "wavedec3", "wavedec", "wavedec2_bwd"):
+            taps = ptwt_amd._wavelets.host_taps(wavelet)
+            if is_bwd:
+                lbufs = [b.detach() for b in bufs]  # (the launch leg below calls the engine directly; `step` keeps the leaves)
+            mode_id = _engine.MODE_IDS[mode]
+            if first_kid in (_engine.KID_PYRAMID, _engine.KID_SMALL):
+                fused_levels = len(_engine.ENGINE.analysis_pyramid(lbufs[0], taps[0], taps[1], mode_id, level))
+                launch = lambda b: _engine.ENGINE.analysis_pyramid(b, taps[0], taps[1], mode_id, level)  # noqa: E731
+            elif first_kid == _engine.KID_PAIR:
+                fused_levels = 2
+                launch = lambda b: _engine.ENGINE.analysis_pair(b, taps[0], taps[1], mode_id)  # noqa: E731
+            elif first_kid == _engine.KID_LONG:
+                fused_levels = len(_engine.ENGINE.analysis_tail(lbufs[0], taps[0], taps[1], mode_id, level))
+                launch = lambda b: _engine.ENGINE.analysis_tail(b, taps[0], taps[1], mode_id, level)  # noqa: E731
+            else:
+                launch = lambda b: _engine.ENGINE.analysis(b, taps[0], taps[1], mode_id)  # noqa: E731
+        if launch is not None:
+            for i in range(5):
                 launch(lbufs[i % len(lbufs)])
-            e1.record()
             sync()
-            batches.append(e0.elapsed_time(e1) / 20)
-        lvl1_b2b_ms, lvl1_b2b_min = statistics.median(batches), min(batches)
+            batches = []
+            for _b in range(10):
+                e0, e1 = new_event(), new_event()
+                e0.record()
+                for i in range(20):
+                    launch(lbufs[i % len(lbufs)])
+                e1.record()
+                sync()
+                batches.append(e0.elapsed_time(e1) / 20)
+            lvl1_b2b_ms, lvl1_b2b_min = statistics.median(batches), min(batches)
 
-    # The K timed steps drop every result, so the caching allocator hands each step the SAME output block and part of the rewritten
-    # output lives in the 256 MiB Infinity Cache.  Second figure, reported next to the headline: the same K steps with the last
-    # `--buffers` results kept alive, i.e. rotating output sets as well as rotating inputs (config 2: ~8 % slower).
-    # (these two loops run AFTER the roofline legs: the rotating loop leaves three freed output sets in the caching allocator, and the
-    # launches that follow would cycle through them — the dominant-kernel leg then measured 0.1076 ms against 0.1048 ms per whole call
-    # and failed its own consistency check)
-    if os.environ.get("MIFWT_BENCH_GC") != "1":
-        gc.disable()
-    held = [None] * max(1, args.buffers)
-    for i in range(max(len(held), min(args.warmup, 10))):
-        held[i % len(held)] = step(i)
-    sync()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        held[i % len(held)] = step(i)
-    sync()
-    rotating_ms = (time.perf_counter() - t1) / args.steps * 1e3
-    del held
-    gc.enable()
-    # ... and with the interpreter's cyclic collector left on (how BENCH_r01 / r02 were timed)
-    for i in range(3):
-        step(i)
-    sync()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    sync()
-    gc_on_ms = (time.perf_counter() - t1) / args.steps * 1e3
-
+        # The K timed steps drop every result, so the caching allocator hands each step the SAME output block and part of the rewritten
+        # output lives in the 256 MiB Infinity Cache.  Second figure, reported next to the headline: the same K steps with the last
+        # `--buffers` results kept alive, i.e. rotating output sets as well as rotating inputs (config 2: ~8 % slower).
+        # (these two loops run AFTER the roofline legs: the rotating loop leaves three freed output sets in the caching allocator, and the
+        # launches that follow would cycle through them — the dominant-kernel leg then measured 0.1076 ms against 0.1048 ms per whole call
+        # and failed its own consistency check)
+        if os.environ.get("MIFWT_BENCH_GC") != "1":
+            gc.disable()
+        held = [None] * max(1, args.buffers)
+        for i in range(max(len(held), min(args.warmup, 10))):
+            held[i % len(held)] = step(i)
+        sync()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            held[i % len(held)] = step(i)
+        sync()
+        rotating_ms = (time.perf_counter() - t1) / args.steps * 1e3
+        del held
+        gc.enable()
+        # ... and with the interpreter's cyclic collector left on (how BENCH_r01 / r02 were timed)
+        for i in range(3):
+            step(i)
+        sync()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            step(i)
+        sync()
+        gc_on_ms = (time.perf_counter() - t1) / args.steps * 1e3
 
     # Optional, outside the timed region (N > 1): what replicating the coefficients on every rank would cost — one
     # all_gather_into_tensor per level buffer over RCCL / xGMI (ptwt_amd.distributed.gather_coeffs).  Reported, never part
@@ -726,7 +773,7 @@ def main():
     # configuration), max over ranks, and the RCCL gather of its coefficient lists (north_star: "RCCL over xGMI used only to gather the
     # coefficient lists"), timed on its own.  Reported under "config4_shard", never part of `value`.
     shard_info = None
-    if distributed and not args.no_secondary and args.workload in SCALING_SHARD:
+    if distributed and args.full and not args.no_secondary and args.workload in SCALING_SHARD:
         shard_info = scaling_shard_leg(SCALING_SHARD[args.workload], dev, dist, backend, world)
 
     if rank == 0:
@@ -736,48 +783,6 @@ def main():
         comp_b, perlvl_b, lvl1_b, pair_b = algorithmic_bytes(shape[0], shape[1:], flen, level, esize)
         if is_bwd:  # the backward reads every coefficient's gradient once and writes the input's gradient once: the same bytes again
             comp_b, perlvl_b = 2 * comp_b, 2 * perlvl_b
-        # dominant kernel = the level-1 analysis launch (largest signal extent); durations from HIP events
-        # recorded on the launch stream inside the timed region
-        lvl1 = [s.elapsed_time(e) for (tag, kid, ext, s, e) in events if tag in ("fwd", "inv") and tuple(ext) == tuple(shape[1:])]
-        per_level_ms = {}
-        for tag, kid, ext, s, e in events:
-            per_level_ms.setdefault(("adjoint " if tag.endswith("_adj") else "") + "x".join(map(str, ext)), []).append(s.elapsed_time(e))
-        kid1 = next((kid for (tag, kid, ext, s, e) in events if tag in ("fwd", "inv") and tuple(ext) == tuple(shape[1:])), -1)
-        if kid1 == _engine.KID_PAIR:
-            lvl1_b = pair_b
-        if kid1 == _engine.KID_INV_PYRAMID:
-            fused_levels = min(3, level)
-        if kid1 in (_engine.KID_PYRAMID, _engine.KID_LONG, _engine.KID_SMALL, _engine.KID_INV_PYRAMID, _engine.KID_INV_SMALL):
-            # input + the detail bands of the fused levels + the approximation of the last fused one (a reconstruction: the same bytes,
-            # read and written the other way round)
-            lvl1_b = algorithmic_bytes(shape[0], shape[1:], flen, fused_levels, esize)[0]
-        klabel = {1: "dwt2_fwd_stream_kernel (level 1)", 7: "dwt2_fwd_tile_kernel (level 1)", 0: "generic axis kernels (level 1)",
-                  3: "streaming axis kernels (level 1)", 5: "composed 3-D level 1: fused 2-D kernel over all depth slices + depth pass (two launches; traffic = both)", 9: "dwt3_fwd_tile_kernel (level 1)", 24: "dwt3_fwd_walk_kernel (level 1)", 25: "idwt3_walk_kernel (finest level)",
-                  11: "dwt2_fwd_mfma_walk_kernel (level 1)", 23: "idwt2_mfma_walk_kernel (finest level)",
-                  12: ("dwt2_fwd_roll_kernel" if flen >= 8 else "dwt2_fwd_pair_kernel") + " (levels 1+2 in one launch)",
-                  16: f"dwt2_fwd_pyr_kernel (levels 1-{fused_levels} in one launch)",
-                  17: f"dwt1_long_kernel (levels 1-{fused_levels} in one launch)",
-                  20: f"dwt2_fwd_small_kernel (levels 1-{fused_levels} in one launch, a workgroup per image)",
-                  22: f"idwt2_pyr_kernel (the {fused_levels} finest synthesis levels in one launch)",
-                  21: f"idwt2_small_kernel (all {fused_levels} synthesis levels in one launch, a workgroup per image)",
-                  13: "idwt2_pair_kernel (two synthesis levels in one launch)", 8: "idwt2_tile_kernel (finest level)",
-                  2: "dwt2_inv_stream_kernel (finest level)", 10: "idwt3_tile_kernel (finest level)", 6: "depth pass + fused 2-D planes (finest level)",
-                  18: "idwt1_long_kernel (the finest levels in one launch)", 15: "idwt1_tail_kernel (the coarse levels in one launch)",
-                  4: "streaming axis kernels (finest level)"}.get(kid1, f"kernel id {kid1} (level 1)")
-        per_launch_event_ms = sum(lvl1) / max(1, len(lvl1))
-        avg_ms = lvl1_b2b_ms if lvl1_b2b_ms else per_launch_event_ms
-        timing_note = ("median of 10 batches of 20 back-to-back launches of that kernel on the launch stream, one HIP event pair per batch "
-                       f"(same rotating inputs; independent of --steps); with an event pair around every launch inside whole calls: {per_launch_event_ms:.4f} ms")
-        # (one fixed definition: the median 20-launch batch, also for calls that ARE one launch — round 3 took the better of this and
-        # ms_per_step for those, which biased the fraction towards the optimistic figure; both are in the line)
-        achieved = lvl1_b / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        traffic, traffic_src = profiled_traffic(args.workload, klabel)
-        # the dominant kernel is one launch of a step: its steady-state duration cannot exceed the step's
-        # (two separately timed loops of the same launches differ by 2-3 % from run to run — 0.1060 against 0.1037 ms in one round-4 run —
-        # so the flag allows 5 %, recorded in the line as consistency_slack; beyond it `frac` is null and the figure moves to
-        # `frac_unchecked`)
-        kConsistencySlack = 1.05
-        consistent = avg_ms <= ms_per_step * kConsistencySlack
         result = {
             "metric": "Msamples/s",
             "value": round(samples_per_step / (elapsed / args.steps) / 1e6, 1),
@@ -805,14 +810,60 @@ def main():
                 "per_level_bytes": perlvl_b,
                 "achieved_GBps_compulsory": round(comp_b / (ms_per_step * 1e-3) / 1e9, 1),
                 "frac_of_hbm_peak": round(comp_b / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            },
+        }
+        if args.full:
+            # dominant kernel = the level-1 analysis launch (largest signal extent); durations from HIP events
+            # recorded on the launch stream inside the timed region
+            lvl1 = [s.elapsed_time(e) for (tag, kid, ext, s, e) in events if tag in ("fwd", "inv") and tuple(ext) == tuple(shape[1:])]
+            per_level_ms = {}
+            for tag, kid, ext, s, e in events:
+                per_level_ms.setdefault(("adjoint " if tag.endswith("_adj") else "") + "x".join(map(str, ext)), []).append(s.elapsed_time(e))
+            kid1 = next((kid for (tag, kid, ext, s, e) in events if tag in ("fwd", "inv") and tuple(ext) == tuple(shape[1:])), -1)
+            if kid1 == _engine.KID_PAIR:
+                lvl1_b = pair_b
+            if kid1 == _engine.KID_INV_PYRAMID:
+                fused_levels = min(3, level)
+            if kid1 in (_engine.KID_PYRAMID, _engine.KID_LONG, _engine.KID_SMALL, _engine.KID_INV_PYRAMID, _engine.KID_INV_SMALL):
+                # input + the detail bands of the fused levels + the approximation of the last fused one (a reconstruction: the same bytes,
+                # read and written the other way round)
+                lvl1_b = algorithmic_bytes(shape[0], shape[1:], flen, fused_levels, esize)[0]
+            klabel = {1: "dwt2_fwd_stream_kernel (level 1)", 7: "dwt2_fwd_tile_kernel (level 1)", 0: "generic axis kernels (level 1)",
+                      3: "streaming axis kernels (level 1)", 5: "composed 3-D level 1: fused 2-D kernel over all depth slices + depth pass (two launches; traffic = both)", 9: "dwt3_fwd_tile_kernel (level 1)", 24: "dwt3_fwd_walk_kernel (level 1)", 25: "idwt3_walk_kernel (finest level)",
+                      11: "dwt2_fwd_mfma_walk_kernel (level 1)", 23: "idwt2_mfma_walk_kernel (finest level)",
+                      12: ("dwt2_fwd_roll_kernel" if flen >= 8 else "dwt2_fwd_pair_kernel") + " (levels 1+2 in one launch)",
+                      16: f"dwt2_fwd_pyr_kernel (levels 1-{fused_levels} in one launch)",
+                      17: f"dwt1_long_kernel (levels 1-{fused_levels} in one launch)",
+                      20: f"dwt2_fwd_small_kernel (levels 1-{fused_levels} in one launch, a workgroup per image)",
+                      22: f"idwt2_pyr_kernel (the {fused_levels} finest synthesis levels in one launch)",
+                      21: f"idwt2_small_kernel (all {fused_levels} synthesis levels in one launch, a workgroup per image)",
+                      13: "idwt2_pair_kernel (two synthesis levels in one launch)", 8: "idwt2_tile_kernel (finest level)",
+                      2: "dwt2_inv_stream_kernel (finest level)", 10: "idwt3_tile_kernel (finest level)", 6: "depth pass + fused 2-D planes (finest level)",
+                      18: "idwt1_long_kernel (the finest levels in one launch)", 15: "idwt1_tail_kernel (the coarse levels in one launch)",
+                      4: "streaming axis kernels (finest level)"}.get(kid1, f"kernel id {kid1} (level 1)")
+            per_launch_event_ms = sum(lvl1) / max(1, len(lvl1))
+            avg_ms = lvl1_b2b_ms if lvl1_b2b_ms else per_launch_event_ms
+            timing_note = ("median of 10 batches of 20 back-to-back launches of that kernel on the launch stream, one HIP event pair per batch "
+                           f"(same rotating inputs; independent of --steps); with an event pair around every launch inside whole calls: {per_launch_event_ms:.4f} ms")
+            # (one fixed definition: the median 20-launch batch, also for calls that ARE one launch — round 3 took the better of this and
+            # ms_per_step for those, which biased the fraction towards the optimistic figure; both are in the line)
+            achieved = lvl1_b / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            traffic, traffic_src = profiled_traffic(args.workload, klabel)
+            # the dominant kernel is one launch of a step: its steady-state duration cannot exceed the step's
+            # (two separately timed loops of the same launches differ by 2-3 % from run to run — 0.1060 against 0.1037 ms in one round-4 run —
+            # so the flag allows 5 %, recorded in the line as consistency_slack; beyond it `frac` is null and the figure moves to
+            # `frac_unchecked`)
+            kConsistencySlack = 1.05
+            consistent = avg_ms <= ms_per_step * kConsistencySlack
+            result["whole_call"].update({
                 "level_kernel_ms": {k: round(sum(v) / len(v), 4) for k, v in per_level_ms.items()},
                 "rotating_outputs_ms": round(rotating_ms, 4),
                 "rotating_outputs_frac_of_hbm_peak": round(comp_b / (rotating_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                 "rotating_outputs_note": f"the same K steps with the last {max(1, args.buffers)} results kept alive (rotating output sets); ms_per_step drops "
                                          "every result, so each step rewrites one output allocation and part of it stays in the 256 MiB Infinity Cache",
                 "gc_enabled_ms": round(gc_on_ms, 4),
-            },
-            "roofline": {
+            })
+            result["roofline"] = {
                 "kernel": klabel,
                 "bound": "hbm",
                 "achieved": round(achieved, 1),
@@ -830,20 +881,19 @@ def main():
                 "timing": timing_note,
                 "traffic": traffic,
                 "traffic_source": (traffic_src + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE per launch of this kernel, not measured in this run)") if traffic_src else None,
-            },
-        }
+            }
         if gather_info is not None:
             result["coefficient_gather"] = gather_info
         if shard_info is not None:
             result["config4_shard"] = shard_info
-        if world == 1 and not args.no_secondary and args.workload == "wavedec2_db4_L3_64x1024x1024_f32" and DEVICE_KIND == "cuda":
+        if args.full and world == 1 and not args.no_secondary and args.workload == "wavedec2_db4_L3_64x1024x1024_f32" and DEVICE_KIND == "cuda":
             del bufs
             torch.cuda.empty_cache()
             if os.environ.get("MIFWT_BENCH_GC") != "1":
                 gc.disable()  # (as in the headline loop: a collector pass inside a 60 ms loop is half its time)
             result["secondary"] = secondary_lines(dev)
             gc.enable()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(fn_name, shape, wavelet, level, mode, dtype)
         print(json.dumps(result), flush=True)
     if distributed:
