@@ -367,8 +367,8 @@ bool border2_fits(const mifwt_level_desc* d, int* threads, size_t* lds) {
 }
 
 template <typename T, int ND>
-int launch_border(const mifwt_level_desc* d, const void* g_approx, const void* const* g_details, void* g_x, const double* lo,
-                  const double* hi, hipStream_t stream) {
+int launch_border(const mifwt_level_desc* d, const void* g_approx, const void* const* g_details, void* g_x, LevelTaps t,
+                  hipStream_t stream) {
   BorderArgs<T, ND> a;
   a.gband[0] = static_cast<const T*>(g_approx);
   for (int s = 1; s < (1 << ND); ++s) a.gband[s] = static_cast<const T*>(g_details[s - 1]);
@@ -406,10 +406,10 @@ int launch_border(const mifwt_level_desc* d, const void* g_approx, const void* c
     a.dv_n[i] = make_fastdiv((uint32_t)a.N[i]);
   }
   for (int m = 0; m < kMaxTaps; ++m) {
-    a.lo[m] = m < a.L ? (T)lo[m] : (T)0;
-    a.hi[m] = m < a.L ? (T)hi[m] : (T)0;
+    a.lo[m] = m < a.L ? (T)t.tap_lo(m) : (T)0;
+    a.hi[m] = m < a.L ? (T)t.tap_hi(m) : (T)0;
   }
-  a.dt = dev_tap_arg(a.L);
+  a.dt = t.dev_arg(a.L);
   if (per_image == 0 || d->batch == 0) return MIFWT_OK;
   if constexpr (ND == 2) {
     int threads = 0;
@@ -456,14 +456,14 @@ bool adjoint_border_supported(const mifwt_level_desc* d) {
   return (box - inner) * kLanesPerSample < (int64_t(1) << 31);  // 32-bit sample indices inside one batch element
 }
 
-int adjoint_border(const mifwt_level_desc* d, const void* g_approx, const void* const* g_details, void* g_x, const double* lo,
-                   const double* hi, hipStream_t stream) {
+int adjoint_border(const mifwt_level_desc* d, const void* g_approx, const void* const* g_details, void* g_x, LevelTaps t,
+                   hipStream_t stream) {
   if (!adjoint_border_supported(d)) return MIFWT_ERR_UNSUPPORTED;
   const bool f64 = d->dtype == MIFWT_F64;
   switch (d->ndim) {
-    case 1: return f64 ? launch_border<double, 1>(d, g_approx, g_details, g_x, lo, hi, stream) : launch_border<float, 1>(d, g_approx, g_details, g_x, lo, hi, stream);
-    case 2: return f64 ? launch_border<double, 2>(d, g_approx, g_details, g_x, lo, hi, stream) : launch_border<float, 2>(d, g_approx, g_details, g_x, lo, hi, stream);
-    default: return f64 ? launch_border<double, 3>(d, g_approx, g_details, g_x, lo, hi, stream) : launch_border<float, 3>(d, g_approx, g_details, g_x, lo, hi, stream);
+    case 1: return f64 ? launch_border<double, 1>(d, g_approx, g_details, g_x, t, stream) : launch_border<float, 1>(d, g_approx, g_details, g_x, t, stream);
+    case 2: return f64 ? launch_border<double, 2>(d, g_approx, g_details, g_x, t, stream) : launch_border<float, 2>(d, g_approx, g_details, g_x, t, stream);
+    default: return f64 ? launch_border<double, 3>(d, g_approx, g_details, g_x, t, stream) : launch_border<float, 3>(d, g_approx, g_details, g_x, t, stream);
   }
 }
 

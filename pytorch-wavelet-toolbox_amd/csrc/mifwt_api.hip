@@ -83,8 +83,8 @@ inline void pad_strides(const int64_t src[1 + MIFWT_MAX_NDIM], int ndim, int64_t
   for (int i = 0; i < 4; ++i) dst[i] = i <= ndim ? src[i] : 0;
 }
 
-int generic_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-                const double* hi, void* ws, hipStream_t stream) {
+int generic_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps taps, void* ws,
+                hipStream_t stream) {
   Stage st[MIFWT_MAX_NDIM];
   const int ns = plan_fwd(d, st);
   const int64_t esz = elem_size(d->dtype);
@@ -131,8 +131,7 @@ int generic_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* co
         memcpy(jb.out0_stride, nxt_stride[s], sizeof(int64_t) * 4);
         memcpy(jb.out1_stride, nxt_stride[s | bit], sizeof(int64_t) * 4);
       }
-      const int rc = launch_axis_fwd(d->dtype, jobs, nj, out_ext, 1 + a, d->sig_extent[a], d->mode, d->filt_len, lo,
-                                     hi, stream);
+      const int rc = launch_axis_fwd(d->dtype, jobs, nj, out_ext, 1 + a, d->sig_extent[a], d->mode, d->filt_len, taps, stream);
       if (rc != MIFWT_OK) return rc;
     }
     ncur *= 2;
@@ -147,9 +146,9 @@ int generic_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* co
 }
 
 // adjoint == true: the transpose of the generic ANALYSIS of this descriptor (same pass structure as the
-// synthesis: band pairs in, signal-extent arrays out; lo / hi are then the DEC taps and the halo is folded back).
-int generic_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y,
-                const double* lo, const double* hi, void* ws, hipStream_t stream, bool adjoint = false) {
+// synthesis: band pairs in, signal-extent arrays out; taps are then the DEC taps and the halo is folded back).
+int generic_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps taps, void* ws,
+                hipStream_t stream, bool adjoint = false) {
   Stage st[MIFWT_MAX_NDIM];
   plan_inv(d, st);
   const int64_t esz = elem_size(d->dtype);
@@ -192,8 +191,8 @@ int generic_inv(const mifwt_level_desc* d, const void* approx, const void* const
       memcpy(jb.out0_stride, nxt_stride[s], sizeof(int64_t) * 4);
     }
     const int rc = adjoint ? launch_axis_adj(d->dtype, jobs, nnext, out_ext, 1 + a, d->coef_extent[a], d->sig_extent[a],
-                                             d->mode, d->filt_len, lo, hi, stream)
-                           : launch_axis_inv(d->dtype, jobs, nnext, out_ext, 1 + a, d->coef_extent[a], d->filt_len, lo, hi, stream);
+                                             d->mode, d->filt_len, taps, stream)
+                           : launch_axis_inv(d->dtype, jobs, nnext, out_ext, 1 + a, d->coef_extent[a], d->filt_len, taps, stream);
     if (rc != MIFWT_OK) return rc;
     ncur = nnext;
     for (int s = 0; s < ncur; ++s) {
@@ -296,7 +295,6 @@ namespace mifwt {
 extern unsigned long long* g_pyr_prof;
 int g_options[16] = {0};
 unsigned long long g_launch_counts[16] = {0};
-thread_local BatchSplit g_batch_split = {0, 0};
 }
 
 extern "C" {
@@ -340,296 +338,223 @@ static mifwt_level_desc as_zero_mode(const mifwt_level_desc* desc) {
   return z;
 }
 
+// DEVICE-RESIDENT TAPS (include/mifwt.h): the _dtaps entry points and mifwt_dwt1_*_outer hand the device arrays to the launchers in a
+// LevelTaps (mifwt_common.h); nothing here reads them.  The kernel ids whose kernels read them: LDS tiles (7 / 8), one level through the
+// streaming kernels (16 / 22; in an analysis adjoint also the border kernels that follow) and the streaming axis passes (3 / 4: 1-D
+// levels and the per-axis maps of the tap gradients).  Every other kernel, the composed 3-D route (5 / 6) among them, takes host taps
+// only: a device-tap call that would go there runs on the generic passes (id 0), which read device taps too.
+static bool reads_device_taps(int kid) {
+  return kid == kDwt2FwdTile || kid == kDwt2InvTile || kid == kDwt2FwdPyr || kid == kDwt2InvPyr || kid == kDwt1FwdRow || kid == kDwt1InvRow;
+}
+
+// the descriptor check of a level call, direction as in mifwt_kernel_id (3 runs as the zero-mode analysis level of desc's extents)
+static int validate_call(const mifwt_level_desc* desc, int direction) {
+  if (direction != 3) return validate(desc, direction == 2 ? 0 : direction);
+  if (!desc) return MIFWT_ERR_BADARG;
+  const mifwt_level_desc z = as_zero_mode(desc);
+  return validate(&z, 0);
+}
+
+// Which kernel serves a (validated) level call; direction 2 / 3 = adjoint of the analysis / synthesis level described by desc.  A
+// zero-mode analysis adjoint IS a synthesis level (reversed dec taps) and every synthesis adjoint IS a zero-mode analysis level
+// (reversed rec taps), so they ride on the fast kernels; other boundary modes take the synthesis launch plus the border kernel where
+// that applies, else the generic adjoint passes.  Device taps (dev): the same kernel where it reads them, else the generic passes.
+static int route(const mifwt_level_desc* desc, int direction, bool dev) {
+  int kid;
+  if (direction == 2) {
+    kid = desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc) ? pick_kernel(desc, 1) : kGeneric;
+  } else if (direction == 3) {
+    const mifwt_level_desc z = as_zero_mode(desc);
+    kid = pick_kernel(&z, 0);
+  } else {
+    kid = pick_kernel(desc, direction);
+  }
+  return dev && !reads_device_taps(kid) ? kGeneric : kid;
+}
+
+// (scratch does not depend on the boundary mode: an analysis adjoint needs that of a synthesis level, a synthesis adjoint that of an
+// analysis level)
+static size_t level_ws(const mifwt_level_desc* desc, int direction, bool dev) {
+  if (validate_call(desc, direction) != MIFWT_OK) return 0;
+  return route_ws(desc, direction == 0 || direction == 3 ? 0 : 1, route(desc, direction, dev));
+}
+
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction) {
-  if (direction == 2) {
-    const int rc = validate(desc, 0);
-    if (rc != MIFWT_OK) return rc;
-    // (boundary extensions: the same launch over the whole signal + the border kernel, mifwt_adjoint_border.hip)
-    return desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc) ? pick_kernel(desc, 1) : kGeneric;
-  }
-  if (direction == 3) {
-    const mifwt_level_desc z = as_zero_mode(desc);
-    const int rc = validate(&z, 0);
-    if (rc != MIFWT_OK) return rc;
-    return pick_kernel(&z, 0);
-  }
-  const int rc = validate(desc, direction);
-  if (rc != MIFWT_OK) return rc;
-  return pick_kernel(desc, direction);
+  const int rc = validate_call(desc, direction);
+  return rc != MIFWT_OK ? rc : route(desc, direction, false);
 }
 
-// direction 2 / 3 = adjoint of the analysis / synthesis level described by desc.  A zero-mode analysis adjoint IS a
-// synthesis level (reversed dec taps) and every synthesis adjoint IS a zero-mode analysis level (reversed rec
-// taps), so they ride on the fast kernels; other boundary modes fold their halo back in the generic adjoint passes.
-size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction) {
-  if (direction == 2) {
-    if (validate(desc, 0) != MIFWT_OK) return 0;
-    if (desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc)) return route_ws(desc, 1, pick_kernel(desc, 1));
-    return generic_ws(desc, 1);
-  }
-  if (direction == 3) {
-    const mifwt_level_desc z = as_zero_mode(desc);
-    if (validate(&z, 0) != MIFWT_OK) return 0;
-    return route_ws(&z, 0, pick_kernel(&z, 0));
-  }
-  if (validate(desc, direction) != MIFWT_OK) return 0;
-  return route_ws(desc, direction, pick_kernel(desc, direction));
+size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction) { return level_ws(desc, direction, false); }
+
+int mifwt_kernel_id_dtaps(const mifwt_level_desc* desc, int direction) {
+  if (direction < 0 || direction > 3) return MIFWT_ERR_BADARG;
+  const int rc = validate_call(desc, direction);
+  return rc != MIFWT_OK ? rc : route(desc, direction, true);
 }
 
-static int run_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details,
-                   const double* dec_lo, const double* dec_hi, void* workspace, size_t workspace_bytes,
-                   void* stream) {
+size_t mifwt_workspace_bytes_dtaps(const mifwt_level_desc* desc, int direction) {
+  return direction < 0 || direction > 3 ? 0 : level_ws(desc, direction, true);
+}
+
+// the filter pair with its taps in reverse order (the adjoints run as levels of the other kind with reversed taps): host taps are
+// copied into buf, device taps flip rev
+static LevelTaps reversed(LevelTaps t, int L, double (&buf)[2][MIFWT_MAX_FILT]) {
+  if (t.dev) return {t.lo, t.hi, true, t.rev ^ 1};
+  for (int j = 0; j < L; ++j) {
+    buf[0][j] = t.tap_lo(L - 1 - j);
+    buf[1][j] = t.tap_hi(L - 1 - j);
+  }
+  return {buf[0], buf[1], false, 0};
+}
+
+// ---- the four level operations, for host taps (mifwt_dwt_*) and device taps (mifwt_dwt_*_dtaps) alike ------------------------------
+static int level_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, LevelTaps dec, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   int rc = validate(desc, 0);
   if (rc != MIFWT_OK) return rc;
-  if (!x || !approx || !details || !dec_lo || !dec_hi) return MIFWT_ERR_BADARG;
+  if (!x || !approx || !details || !dec.lo || !dec.hi) return MIFWT_ERR_BADARG;
   for (int s = 1; s < (1 << desc->ndim); ++s)
     if (!details[s - 1]) return MIFWT_ERR_BADARG;
   if (desc->batch == 0) return MIFWT_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int kid = pick_kernel(desc, 0);
+  const int kid = route(desc, 0, dec.dev);
   const size_t need = route_ws(desc, 0, kid);
   if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  switch (kid) {
-    case kDwt2FwdStream: return dwt2_fwd_stream(desc, x, approx, details, dec_lo, dec_hi, st);
-    case kDwt2FwdTile: return dwt2_fwd_tile(desc, x, approx, details, dec_lo, dec_hi, st);
-    case kDwt2FwdMfma: return dwt2_fwd_mfma(desc, x, approx, details, dec_lo, dec_hi, st);
-    case kDwt2FwdPyr: return dwt2_fwd_fused(desc, x, approx, details, dec_lo, dec_hi, st);  // (one level through the streaming kernel)
-    case kDwt3FwdTile: return dwt3_fwd_tile(desc, x, approx, details, dec_lo, dec_hi, st);
-    case kDwt3FwdWalk: return dwt3_fwd_walk(desc, x, approx, details, dec_lo, dec_hi, st);
-    case kDwt3FwdStream: return plane3_fwd(desc, x, approx, details, dec_lo, dec_hi, workspace, st);
-    case kDwt1FwdRow: return rows_fwd(desc, x, approx, details, dec_lo, dec_hi, workspace, st);
+  switch (kid) {  // the launchers that can read device taps take the LevelTaps ...
+    case kGeneric: return generic_fwd(desc, x, approx, details, dec, workspace, st);
+    case kDwt2FwdTile: return dwt2_fwd_tile(desc, x, approx, details, dec, st);
+    case kDwt2FwdPyr: return dwt2_fwd_fused(desc, x, approx, details, dec, st);  // (one level through the streaming kernel)
+    case kDwt1FwdRow: return rows_fwd(desc, x, approx, details, dec, workspace, st);
     default: break;
   }
-  return generic_fwd(desc, x, approx, details, dec_lo, dec_hi, workspace, st);
+  const double *lo, *hi;  // ... every other one the host arrays
+  if ((rc = dec.host(&lo, &hi)) != MIFWT_OK) return rc;
+  switch (kid) {
+    case kDwt2FwdStream: return dwt2_fwd_stream(desc, x, approx, details, lo, hi, st);
+    case kDwt2FwdMfma: return dwt2_fwd_mfma(desc, x, approx, details, lo, hi, st);
+    case kDwt3FwdTile: return dwt3_fwd_tile(desc, x, approx, details, lo, hi, st);
+    case kDwt3FwdWalk: return dwt3_fwd_walk(desc, x, approx, details, lo, hi, st);
+    case kDwt3FwdStream: return plane3_fwd(desc, x, approx, details, lo, hi, workspace, st);
+    default: return MIFWT_ERR_UNSUPPORTED;
+  }
 }
 
-static int run_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y,
-                   const double* rec_lo, const double* rec_hi, void* workspace, size_t workspace_bytes,
-                   void* stream) {
+static int level_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, LevelTaps rec, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   int rc = validate(desc, 1);
   if (rc != MIFWT_OK) return rc;
-  if (!y || !approx || !details || !rec_lo || !rec_hi) return MIFWT_ERR_BADARG;
+  if (!y || !approx || !details || !rec.lo || !rec.hi) return MIFWT_ERR_BADARG;
   for (int s = 1; s < (1 << desc->ndim); ++s)
     if (!details[s - 1]) return MIFWT_ERR_BADARG;
   if (desc->batch == 0) return MIFWT_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int kid = pick_kernel(desc, 1);
+  const int kid = route(desc, 1, rec.dev);
   const size_t need = route_ws(desc, 1, kid);
   if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  switch (kid) {
-    case kDwt2InvStream: return dwt2_inv_stream(desc, approx, details, y, rec_lo, rec_hi, st);
-    case kDwt2InvTile: return dwt2_inv_tile(desc, approx, details, y, rec_lo, rec_hi, st);
-    case kDwt2InvMfma: return dwt2_inv_mfma(desc, approx, details, y, rec_lo, rec_hi, st);
-    case kDwt2InvPyr: return dwt2_inv_fused(desc, approx, details, y, rec_lo, rec_hi, st);  // (one level through the streaming kernel)
-    case kDwt3InvTile: return dwt3_inv_tile(desc, approx, details, y, rec_lo, rec_hi, st);
-    case kDwt3InvWalk: return dwt3_inv_walk(desc, approx, details, y, rec_lo, rec_hi, st);
-    case kDwt3InvStream: return plane3_inv(desc, approx, details, y, rec_lo, rec_hi, workspace, st);
-    case kDwt1InvRow: return rows_inv(desc, approx, details, y, rec_lo, rec_hi, workspace, st);
+  switch (kid) {  // (as in level_fwd)
+    case kGeneric: return generic_inv(desc, approx, details, y, rec, workspace, st);
+    case kDwt2InvTile: return dwt2_inv_tile(desc, approx, details, y, rec, st);
+    case kDwt2InvPyr: return dwt2_inv_fused(desc, approx, details, y, rec, st);  // (one level through the streaming kernel)
+    case kDwt1InvRow: return rows_inv(desc, approx, details, y, rec, workspace, st);
     default: break;
   }
-  return generic_inv(desc, approx, details, y, rec_lo, rec_hi, workspace, st);
+  const double *lo, *hi;
+  if ((rc = rec.host(&lo, &hi)) != MIFWT_OK) return rc;
+  switch (kid) {
+    case kDwt2InvStream: return dwt2_inv_stream(desc, approx, details, y, lo, hi, st);
+    case kDwt2InvMfma: return dwt2_inv_mfma(desc, approx, details, y, lo, hi, st);
+    case kDwt3InvTile: return dwt3_inv_tile(desc, approx, details, y, lo, hi, st);
+    case kDwt3InvWalk: return dwt3_inv_walk(desc, approx, details, y, lo, hi, st);
+    case kDwt3InvStream: return plane3_inv(desc, approx, details, y, lo, hi, workspace, st);
+    default: return MIFWT_ERR_UNSUPPORTED;
+  }
+}
+
+static int level_fwd_adjoint(const mifwt_level_desc* desc, const void* g_approx, const void* const* g_details, void* g_x, LevelTaps dec,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = validate(desc, 0);
+  if (rc != MIFWT_OK) return rc;
+  if (!g_x || !g_approx || !g_details || !dec.lo || !dec.hi) return MIFWT_ERR_BADARG;
+  for (int s = 1; s < (1 << desc->ndim); ++s)
+    if (!g_details[s - 1]) return MIFWT_ERR_BADARG;
+  if (desc->batch == 0) return MIFWT_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // u[n] = sum_k a[k] h[2k + 1 - n] is the synthesis formula with g[j] = h[L - 1 - j]; its cropped interior [0, 2M - L + 2 - N%2) is
+  // exactly [0, N).  A boundary extension: the interior of the adjoint is the zero-mode adjoint (a sample away from the borders has no
+  // pad position mapped onto it); the samples near a border are recomputed with the pad positions folded back (mifwt_adjoint_border.hip).
+  // Device taps take that route only where its synthesis kernel reads them.
+  const bool synth = dec.dev ? route(desc, 2, true) != kGeneric : desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc);
+  if (!synth) {
+    const size_t need = generic_ws(desc, 1);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
+    return generic_inv(desc, g_approx, g_details, g_x, dec, workspace, st, true);
+  }
+  double buf[2][MIFWT_MAX_FILT];
+  const mifwt_level_desc z = as_zero_mode(desc);
+  rc = level_inv(&z, g_approx, g_details, g_x, reversed(dec, desc->filt_len, buf), workspace, workspace_bytes, stream);
+  if (rc != MIFWT_OK || desc->mode == MIFWT_MODE_ZERO) return rc;
+  return adjoint_border(desc, g_approx, g_details, g_x, dec, st);
+}
+
+static int level_inv_adjoint(const mifwt_level_desc* desc, const void* g_y, void* g_approx, void* const* g_details, LevelTaps rec,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = validate(desc, 1);
+  if (rc != MIFWT_OK) return rc;
+  if (!rec.lo || !rec.hi) return MIFWT_ERR_BADARG;
+  // g_a[k] = sum_n g_y[n] g[n + L - 2 - 2k] is the zero-mode analysis formula with h[m] = g[L - 1 - m]; its
+  // output extent floor((Nout + L - 1) / 2) is exactly M
+  double buf[2][MIFWT_MAX_FILT];
+  const mifwt_level_desc z = as_zero_mode(desc);
+  return level_fwd(&z, g_y, g_approx, g_details, reversed(rec, desc->filt_len, buf), workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details,
                   const double* dec_lo, const double* dec_hi, void* workspace, size_t workspace_bytes,
                   void* stream) {
-  return run_fwd(desc, x, approx, details, dec_lo, dec_hi, workspace, workspace_bytes, stream);
+  return level_fwd(desc, x, approx, details, {dec_lo, dec_hi, false, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y,
                   const double* rec_lo, const double* rec_hi, void* workspace, size_t workspace_bytes,
                   void* stream) {
-  return run_inv(desc, approx, details, y, rec_lo, rec_hi, workspace, workspace_bytes, stream);
+  return level_inv(desc, approx, details, y, {rec_lo, rec_hi, false, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_fwd_adjoint(const mifwt_level_desc* desc, const void* g_approx, const void* const* g_details, void* g_x,
                           const double* dec_lo, const double* dec_hi, void* workspace, size_t workspace_bytes,
                           void* stream) {
-  int rc = validate(desc, 0);
-  if (rc != MIFWT_OK) return rc;
-  if (!g_x || !g_approx || !g_details || !dec_lo || !dec_hi) return MIFWT_ERR_BADARG;
-  const int L = desc->filt_len;
-  const bool fold_back = desc->mode != MIFWT_MODE_ZERO && adjoint_border_supported(desc);
-  if (desc->mode == MIFWT_MODE_ZERO || fold_back) {
-    // u[n] = sum_k a[k] h[2k + 1 - n] is the synthesis formula with g[j] = h[L - 1 - j]; its cropped interior
-    // [0, 2M - L + 2 - N%2) is exactly [0, N)
-    double lo[MIFWT_MAX_FILT], hi[MIFWT_MAX_FILT];
-    for (int j = 0; j < L; ++j) {
-      lo[j] = dec_lo[L - 1 - j];
-      hi[j] = dec_hi[L - 1 - j];
-    }
-    if (!fold_back) return run_inv(desc, g_approx, g_details, g_x, lo, hi, workspace, workspace_bytes, stream);
-    // a boundary extension: the interior of the adjoint is the zero-mode adjoint (a sample away from the borders has no pad position
-    // mapped onto it); the samples near a border are recomputed with the pad positions folded back (mifwt_adjoint_border.hip)
-    for (int s = 1; s < (1 << desc->ndim); ++s)
-      if (!g_details[s - 1]) return MIFWT_ERR_BADARG;
-    const mifwt_level_desc z = as_zero_mode(desc);
-    rc = run_inv(&z, g_approx, g_details, g_x, lo, hi, workspace, workspace_bytes, stream);
-    if (rc != MIFWT_OK || desc->batch == 0) return rc;
-    return adjoint_border(desc, g_approx, g_details, g_x, dec_lo, dec_hi, static_cast<hipStream_t>(stream));
-  }
-  for (int s = 1; s < (1 << desc->ndim); ++s)
-    if (!g_details[s - 1]) return MIFWT_ERR_BADARG;
-  if (desc->batch == 0) return MIFWT_OK;
-  const size_t need = generic_ws(desc, 1);
-  if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  return generic_inv(desc, g_approx, g_details, g_x, dec_lo, dec_hi, workspace, static_cast<hipStream_t>(stream), true);
+  return level_fwd_adjoint(desc, g_approx, g_details, g_x, {dec_lo, dec_hi, false, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_inv_adjoint(const mifwt_level_desc* desc, const void* g_y, void* g_approx, void* const* g_details,
                           const double* rec_lo, const double* rec_hi, void* workspace, size_t workspace_bytes,
                           void* stream) {
-  int rc = validate(desc, 1);
-  if (rc != MIFWT_OK) return rc;
-  if (!rec_lo || !rec_hi) return MIFWT_ERR_BADARG;
-  // g_a[k] = sum_n g_y[n] g[n + L - 2 - 2k] is the zero-mode analysis formula with h[m] = g[L - 1 - m]; its
-  // output extent floor((Nout + L - 1) / 2) is exactly M
-  const int L = desc->filt_len;
-  double lo[MIFWT_MAX_FILT], hi[MIFWT_MAX_FILT];
-  for (int j = 0; j < L; ++j) {
-    lo[j] = rec_lo[L - 1 - j];
-    hi[j] = rec_hi[L - 1 - j];
-  }
-  const mifwt_level_desc z = as_zero_mode(desc);
-  return run_fwd(&z, g_y, g_approx, g_details, lo, hi, workspace, workspace_bytes, stream);
-}
-
-// ---- device-resident taps (include/mifwt.h): the four level operations with the filter read from device memory by the kernels.
-// Nothing here touches the taps on the host.  Round 5: the generic axis passes.  Round 6: the fused 2-D kernels that serve a
-// learnable-wavelet training step on image-sized planes — LDS tiles (ids 7 / 8), one level through the streaming kernels (ids 16 / 22),
-// the border kernels of the analysis adjoint — and the streaming axis passes (ids 3 / 4: 1-D levels and the per-axis maps of the tap
-// gradients; ids 5 / 6: the composed 3-D route) take the same device arrays (DevTapArg, mifwt_common.h); everything else stays on the
-// generic passes.
-namespace {
-struct DtapsScope {
-  DtapsScope(const double* lo, const double* hi, int rev) {
-    mifwt::g_dtaps = {lo, hi, rev};
-    mifwt::g_dtaps_taken = 0;
-  }
-  ~DtapsScope() { mifwt::g_dtaps = {nullptr, nullptr, 0}; }
-  // a fused route must have handed the device taps to every kernel it launched: one that ran on the (zero) host taps is a bug, and loud
-  static int checked(int rc) { return rc == MIFWT_OK && mifwt::g_dtaps_taken == 0 ? MIFWT_ERR_LAUNCH : rc; }
-};
-const double kNoHostTaps[MIFWT_MAX_FILT] = {0};
-// kernel ids whose kernels read DevTapArg
-bool dtaps_fused(int kid) {
-  return kid == kDwt2FwdTile || kid == kDwt2InvTile || kid == kDwt2FwdPyr || kid == kDwt2InvPyr || kid == kDwt1FwdRow || kid == kDwt1InvRow;
-}
-// which kernel serves a device-tap call: that of the host-tap call where it reads device taps (direction 2: also the border kernel),
-// else the generic passes
-int dtaps_kernel(const mifwt_level_desc* desc, int direction) {
-  if (g_options[MIFWT_OPT_FORCE_GENERIC]) return kGeneric;
-  int kid = kGeneric;
-  if (direction == 0 || direction == 1) {
-    kid = pick_kernel(desc, direction);
-  } else if (direction == 2) {
-    if (desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc)) kid = pick_kernel(desc, 1);
-  } else {
-    const mifwt_level_desc z = as_zero_mode(desc);
-    kid = pick_kernel(&z, 0);
-  }
-  return dtaps_fused(kid) ? kid : kGeneric;
-}
-}  // namespace
-
-int mifwt_kernel_id_dtaps(const mifwt_level_desc* desc, int direction) {
-  if (!desc || direction < 0 || direction > 3) return MIFWT_ERR_BADARG;
-  mifwt_level_desc z = *desc;
-  if (direction == 3) z.mode = MIFWT_MODE_ZERO;
-  const int rc = validate(&z, direction == 1 ? 1 : 0);
-  if (rc != MIFWT_OK) return rc;
-  return dtaps_kernel(desc, direction);
-}
-
-size_t mifwt_workspace_bytes_dtaps(const mifwt_level_desc* desc, int direction) {
-  if (direction == 3) {
-    const mifwt_level_desc z = as_zero_mode(desc);
-    if (validate(&z, 0) != MIFWT_OK) return 0;
-    const int kid = dtaps_kernel(desc, 3);
-    return kid == kGeneric ? generic_ws(&z, 0) : route_ws(&z, 0, kid);
-  }
-  if (validate(desc, direction == 1 ? 1 : 0) != MIFWT_OK) return 0;
-  const int kid = dtaps_kernel(desc, direction);
-  if (kid != kGeneric) return route_ws(desc, direction == 0 ? 0 : 1, kid);
-  return generic_ws(desc, direction == 0 ? 0 : 1);
+  return level_inv_adjoint(desc, g_y, g_approx, g_details, {rec_lo, rec_hi, false, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_fwd_dtaps(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* d_dec_lo,
                         const double* d_dec_hi, void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = validate(desc, 0);
-  if (rc != MIFWT_OK) return rc;
-  if (!x || !approx || !details || !d_dec_lo || !d_dec_hi) return MIFWT_ERR_BADARG;
-  for (int s = 1; s < (1 << desc->ndim); ++s)
-    if (!details[s - 1]) return MIFWT_ERR_BADARG;
-  if (desc->batch == 0) return MIFWT_OK;
-  DtapsScope scope(d_dec_lo, d_dec_hi, 0);
-  if (dtaps_kernel(desc, 0) != kGeneric)
-    return DtapsScope::checked(run_fwd(desc, x, approx, details, kNoHostTaps, kNoHostTaps, workspace, workspace_bytes, stream));
-  const size_t need = generic_ws(desc, 0);
-  if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  return generic_fwd(desc, x, approx, details, kNoHostTaps, kNoHostTaps, workspace, static_cast<hipStream_t>(stream));
+  return level_fwd(desc, x, approx, details, {d_dec_lo, d_dec_hi, true, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_inv_dtaps(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* d_rec_lo,
                         const double* d_rec_hi, void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = validate(desc, 1);
-  if (rc != MIFWT_OK) return rc;
-  if (!y || !approx || !details || !d_rec_lo || !d_rec_hi) return MIFWT_ERR_BADARG;
-  for (int s = 1; s < (1 << desc->ndim); ++s)
-    if (!details[s - 1]) return MIFWT_ERR_BADARG;
-  if (desc->batch == 0) return MIFWT_OK;
-  DtapsScope scope(d_rec_lo, d_rec_hi, 0);
-  if (dtaps_kernel(desc, 1) != kGeneric)
-    return DtapsScope::checked(run_inv(desc, approx, details, y, kNoHostTaps, kNoHostTaps, workspace, workspace_bytes, stream));
-  const size_t need = generic_ws(desc, 1);
-  if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  return generic_inv(desc, approx, details, y, kNoHostTaps, kNoHostTaps, workspace, static_cast<hipStream_t>(stream));
+  return level_inv(desc, approx, details, y, {d_rec_lo, d_rec_hi, true, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_fwd_adjoint_dtaps(const mifwt_level_desc* desc, const void* g_approx, const void* const* g_details, void* g_x,
                                 const double* d_dec_lo, const double* d_dec_hi, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = validate(desc, 0);
-  if (rc != MIFWT_OK) return rc;
-  if (!g_x || !g_approx || !g_details || !d_dec_lo || !d_dec_hi) return MIFWT_ERR_BADARG;
-  for (int s = 1; s < (1 << desc->ndim); ++s)
-    if (!g_details[s - 1]) return MIFWT_ERR_BADARG;
-  if (desc->batch == 0) return MIFWT_OK;
-  if (dtaps_kernel(desc, 2) != kGeneric) {
-    // (mifwt_dwt_fwd_adjoint: the synthesis kernel with the dec taps REVERSED over the whole signal, then — a boundary extension — the
-    // border kernel with the dec taps as they are)
-    const mifwt_level_desc z = as_zero_mode(desc);
-    {
-      DtapsScope scope(d_dec_lo, d_dec_hi, 1);
-      rc = DtapsScope::checked(run_inv(&z, g_approx, g_details, g_x, kNoHostTaps, kNoHostTaps, workspace, workspace_bytes, stream));
-    }
-    if (rc != MIFWT_OK || desc->mode == MIFWT_MODE_ZERO) return rc;
-    DtapsScope scope(d_dec_lo, d_dec_hi, 0);
-    return DtapsScope::checked(adjoint_border(desc, g_approx, g_details, g_x, kNoHostTaps, kNoHostTaps, static_cast<hipStream_t>(stream)));
-  }
-  const size_t need = generic_ws(desc, 1);
-  if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  DtapsScope scope(d_dec_lo, d_dec_hi, 0);
-  return generic_inv(desc, g_approx, g_details, g_x, kNoHostTaps, kNoHostTaps, workspace, static_cast<hipStream_t>(stream), true);
+  return level_fwd_adjoint(desc, g_approx, g_details, g_x, {d_dec_lo, d_dec_hi, true, 0}, workspace, workspace_bytes, stream);
 }
 
 int mifwt_dwt_inv_adjoint_dtaps(const mifwt_level_desc* desc, const void* g_y, void* g_approx, void* const* g_details,
                                 const double* d_rec_lo, const double* d_rec_hi, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = validate(desc, 1);
-  if (rc != MIFWT_OK) return rc;
-  if (!g_y || !g_approx || !g_details || !d_rec_lo || !d_rec_hi) return MIFWT_ERR_BADARG;
-  // (a zero-mode analysis level with the rec taps reversed: mifwt_dwt_inv_adjoint)
-  const mifwt_level_desc z = as_zero_mode(desc);
-  rc = validate(&z, 0);
-  if (rc != MIFWT_OK) return rc;
-  for (int s = 1; s < (1 << desc->ndim); ++s)
-    if (!g_details[s - 1]) return MIFWT_ERR_BADARG;
-  if (desc->batch == 0) return MIFWT_OK;
-  DtapsScope scope(d_rec_lo, d_rec_hi, 1);
-  if (dtaps_kernel(desc, 3) != kGeneric)
-    return DtapsScope::checked(run_fwd(&z, g_y, g_approx, g_details, kNoHostTaps, kNoHostTaps, workspace, workspace_bytes, stream));
-  const size_t need = generic_ws(&z, 0);
-  if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;
-  return generic_fwd(&z, g_y, g_approx, g_details, kNoHostTaps, kNoHostTaps, workspace, static_cast<hipStream_t>(stream));
+  return level_inv_adjoint(desc, g_y, g_approx, g_details, {d_rec_lo, d_rec_hi, true, 0}, workspace, workspace_bytes, stream);
+}
+
+// the taps of a call that takes both forms: the device pair where both of its pointers are given, else the host pair (null: neither)
+static LevelTaps host_or_device(const double* lo, const double* hi, const double* d_lo, const double* d_hi) {
+  return d_lo && d_hi ? LevelTaps{d_lo, d_hi, true, 0} : LevelTaps{lo, hi, false, 0};
 }
 
 // One 1-D analysis level along the MIDDLE axis of [batch, n, inner] arrays (inner contiguous) — the streaming outer-axis kernel
@@ -638,8 +563,8 @@ int mifwt_dwt_inv_adjoint_dtaps(const mifwt_level_desc* desc, const void* g_y, v
 int mifwt_dwt1_fwd_outer(int dtype, int64_t batch, int64_t n, int64_t inner, const void* x, int64_t x_batch_stride, int64_t x_axis_stride, void* lo_out,
                          void* hi_out, int64_t out_batch_stride, int64_t out_axis_stride, int mode, int filt_len, const double* dec_lo,
                          const double* dec_hi, const double* d_dec_lo, const double* d_dec_hi, void* stream) {
-  if (!x || !lo_out || !hi_out || batch < 0 || n < 1 || inner < 1) return MIFWT_ERR_BADARG;
-  if (!((dec_lo && dec_hi) || (d_dec_lo && d_dec_hi))) return MIFWT_ERR_BADARG;
+  const LevelTaps taps = host_or_device(dec_lo, dec_hi, d_dec_lo, d_dec_hi);
+  if (!x || !lo_out || !hi_out || !taps.lo || !taps.hi || batch < 0 || n < 1 || inner < 1) return MIFWT_ERR_BADARG;
   if (mode < MIFWT_MODE_ZERO || mode > MIFWT_MODE_SYMMETRIC) return MIFWT_ERR_BADARG;
   if ((dtype != MIFWT_F32 && dtype != MIFWT_F64) || !stream_filter_supported(filt_len)) return MIFWT_ERR_UNSUPPORTED;
   if (batch == 0) return MIFWT_OK;
@@ -660,13 +585,8 @@ int mifwt_dwt1_fwd_outer(int dtype, int64_t batch, int64_t n, int64_t inner, con
   c.inner = inner;
   c.n_in = n;
   c.n_out = (n + filt_len - 1) / 2;
-  c.lo = d_dec_lo ? kNoHostTaps : dec_lo;
-  c.hi = d_dec_lo ? kNoHostTaps : dec_hi;
+  c.taps = taps;
   c.stream = static_cast<hipStream_t>(stream);
-  if (d_dec_lo) {
-    DtapsScope scope(d_dec_lo, d_dec_hi, 0);
-    return DtapsScope::checked(stream_call(dtype, kOuterFwd, c));
-  }
   return stream_call(dtype, kOuterFwd, c);
 }
 
@@ -677,8 +597,8 @@ int mifwt_dwt1_inv_outer(int dtype, int64_t batch, int64_t m, int64_t n_out, int
                          int64_t lo_axis_stride, const void* hi_in, int64_t hi_batch_stride, int64_t hi_axis_stride, void* y, int64_t y_batch_stride,
                          int64_t y_axis_stride, int filt_len, const double* rec_lo, const double* rec_hi, const double* d_rec_lo,
                          const double* d_rec_hi, void* stream) {
-  if (!lo_in || !hi_in || !y || batch < 0 || m < 1 || inner < 1 || n_out < 1) return MIFWT_ERR_BADARG;
-  if (!((rec_lo && rec_hi) || (d_rec_lo && d_rec_hi))) return MIFWT_ERR_BADARG;
+  const LevelTaps taps = host_or_device(rec_lo, rec_hi, d_rec_lo, d_rec_hi);
+  if (!lo_in || !hi_in || !y || !taps.lo || !taps.hi || batch < 0 || m < 1 || inner < 1 || n_out < 1) return MIFWT_ERR_BADARG;
   if (n_out > 2 * m - filt_len + 2 || n_out < 2 * m - filt_len + 1) return MIFWT_ERR_BADARG;
   if ((dtype != MIFWT_F32 && dtype != MIFWT_F64) || !stream_filter_supported(filt_len)) return MIFWT_ERR_UNSUPPORTED;
   if (batch == 0) return MIFWT_OK;
@@ -699,13 +619,8 @@ int mifwt_dwt1_inv_outer(int dtype, int64_t batch, int64_t m, int64_t n_out, int
   c.inner = inner;
   c.n_in = m;
   c.n_out = n_out;
-  c.lo = d_rec_lo ? kNoHostTaps : rec_lo;
-  c.hi = d_rec_lo ? kNoHostTaps : rec_hi;
+  c.taps = taps;
   c.stream = static_cast<hipStream_t>(stream);
-  if (d_rec_lo) {
-    DtapsScope scope(d_rec_lo, d_rec_hi, 0);
-    return DtapsScope::checked(stream_call(dtype, kOuterInv, c));
-  }
   return stream_call(dtype, kOuterInv, c);
 }
 
@@ -775,7 +690,7 @@ int mifwt_dwt2_fwd_pyramid(int nlevels, const mifwt_level_desc* const* descs, co
   if (route == 0) return MIFWT_ERR_UNSUPPORTED;
   if (descs[0]->batch == 0) return MIFWT_OK;
   if (route == 2) return dwt2_fwd_small(nlevels, descs, x, details, approx, dec_lo, dec_hi, static_cast<hipStream_t>(stream));
-  return dwt2_fwd_pyr(nlevels, descs, x, details, approx, dec_lo, dec_hi, static_cast<hipStream_t>(stream));
+  return dwt2_fwd_pyr(nlevels, descs, x, details, approx, {dec_lo, dec_hi, false, 0}, static_cast<hipStream_t>(stream));
 }
 int mifwt_dwt2_fwd_pyramid_schedule(int nlevels, const mifwt_level_desc* const* descs, unsigned int* wg_start, int capacity) {
   if (!descs || !wg_start || nlevels < 1 || nlevels > 3) return MIFWT_ERR_BADARG;
@@ -821,7 +736,7 @@ int mifwt_dwt2_inv_pyramid(int nlevels, const mifwt_level_desc* const* descs, co
     return dwt2_inv_small(nlevels, descs, approx, details, y, rec_lo, rec_hi, static_cast<hipStream_t>(stream));
   }
   if (nlevels > 3 || !dwt2_inv_pyr_supported(nlevels, descs)) return MIFWT_ERR_UNSUPPORTED;
-  return dwt2_inv_pyr(nlevels, descs, approx, details, y, rec_lo, rec_hi, static_cast<hipStream_t>(stream));
+  return dwt2_inv_pyr(nlevels, descs, approx, details, y, {rec_lo, rec_hi, false, 0}, static_cast<hipStream_t>(stream));
 }
 // Two consecutive 2-D synthesis levels in one launch (mifwt_idwt2_pair.hip); d2 describes the coarser level, whose
 // (cropped) output is the approximation of d1 and is never materialised.

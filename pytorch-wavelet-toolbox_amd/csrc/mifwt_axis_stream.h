@@ -485,10 +485,10 @@ int stream_launch(int kind, const StreamCall& c) {  // kind: 0 outer fwd, 1 oute
   a.n_in = (int)c.n_in;
   a.n_out = (int)c.n_out;
   for (int m = 0; m < L; ++m) {
-    a.lo[m] = (A)c.lo[m];
-    a.hi[m] = (A)c.hi[m];
+    a.lo[m] = (A)c.taps.tap_lo(m);
+    a.hi[m] = (A)c.taps.tap_hi(m);
   }
-  a.dt = dev_tap_arg(L);
+  a.dt = c.taps.dev_arg(L);
   int64_t ntasks;
   if (kind < 2) {
     if (c.batch > INT32_MAX) return MIFWT_ERR_UNSUPPORTED;

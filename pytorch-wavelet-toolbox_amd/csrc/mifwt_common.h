@@ -36,12 +36,11 @@ inline int exp_word() { return kDiag ? g_options[MIFWT_OPT_EXP] : 0; }
 extern unsigned long long g_launch_counts[16];  // mifwt_launch_count(): launches per kernel variant (MIFWT_VARIANT_*)
 inline void count_launch(int variant) { __atomic_fetch_add(&g_launch_counts[variant], 1ull, __ATOMIC_RELAXED); }
 
-// Two-level batch for ONE call of the LDS-tile 2-D analysis kernel (thread-local, set and cleared by the 3-D composed route around that
-// call): the input images are `inner` slices per volume, `outer_stride` elements between volumes; inner == 0: off.
+// Two-level batch of the LDS-tile 2-D analysis kernel (dwt2_fwd_tile; the 3-D composed route hands every slice of every volume to one
+// launch): the input images are `inner` slices per volume, `outer_stride` elements between volumes; inner == 0: off.
 struct BatchSplit {
   int64_t inner, outer_stride;
 };
-extern thread_local BatchSplit g_batch_split;
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of a kernel ON A DEVICE: set it once per (kernel, device).  One of these
 // as a function-local static next to each launch; safe from threads that call with the GIL released (two racing threads at worst
@@ -123,29 +122,42 @@ struct AxisJob {
   int64_t in0_stride[4], in1_stride[4], out0_stride[4], out1_stride[4];
 };
 
-// DEVICE-RESIDENT TAPS (round 5): while `g_dtaps.lo` is set (mifwt_*_dtaps entry points, this thread only) the generic axis kernels
-// read their filter from these device arrays of L doubles instead of their launch arguments — a learnable filter bank that lives on
-// the GPU then needs no device-to-host copy, no stream synchronisation, and the calls can be captured into a HIP graph.  `rev`:
-// tap m of the pass is element L - 1 - m of the arrays (the adjoint of a synthesis level is an analysis level with reversed taps).
+// DEVICE-RESIDENT TAPS (mifwt_*_dtaps entry points, mifwt_dwt1_*_outer): the filter of a learnable bank that lives on the GPU is read by
+// the kernels from device arrays of L doubles — no device-to-host copy, no stream synchronisation, and the calls can be captured into a
+// HIP graph.  Kernel parameter types: the generic axis kernels take DeviceTaps, the fused kernels DevTapArg (lo == nullptr: the taps
+// travel by value as before; else the kernel reads the L doubles once, when it starts, into the registers its by-value taps would
+// occupy — same conversions, same packing, bit-identical results).  `rev`: tap m of the pass is element L - 1 - m of the arrays (the
+// adjoint of a synthesis level is an analysis level with reversed taps).
 struct DeviceTaps {
   const double* lo;
   const double* hi;
   int rev;
 };
-extern thread_local DeviceTaps g_dtaps;
-// ... and (round 6) the FUSED kernels that serve the learnable-wavelet training loop: their launch code copies this thread's
-// `g_dtaps` into the kernel arguments (DevTapArg; lo == nullptr: the taps travel by value as before) and the kernel reads the L doubles
-// once, when it starts, into the registers its by-value taps would occupy — same conversions, same packing, bit-identical results.
 struct DevTapArg {
   const double* lo;
   const double* hi;
   int rev, len;
 };
-extern thread_local int g_dtaps_taken;  // launches that copied g_dtaps into their arguments (checked by the mifwt_*_dtaps entry points)
-inline DevTapArg dev_tap_arg(int filt_len) {
-  if (g_dtaps.lo) ++g_dtaps_taken;
-  return {g_dtaps.lo, g_dtaps.hi, g_dtaps.rev, filt_len};
-}
+// A level's filter pair, as the launchers take it: host arrays of L doubles (dev == false), or device arrays the kernels read themselves
+// (dev == true, rev as above).  A launcher whose kernels can read device taps takes a LevelTaps and passes zeros for its by-value taps
+// when the taps are on the device (tap_lo / tap_hi); every other launcher takes host arrays, and host() is the one way to them: it
+// refuses device taps, so no kernel can run on taps it does not see.
+struct LevelTaps {
+  const double* lo;
+  const double* hi;
+  bool dev;
+  int rev;
+  double tap_lo(int m) const { return dev ? 0.0 : lo[m]; }  // by-value tap m (host taps as given: rev applies to device taps only)
+  double tap_hi(int m) const { return dev ? 0.0 : hi[m]; }
+  DeviceTaps dev_taps() const { return dev ? DeviceTaps{lo, hi, rev} : DeviceTaps{nullptr, nullptr, 0}; }
+  DevTapArg dev_arg(int filt_len) const { return dev ? DevTapArg{lo, hi, rev, filt_len} : DevTapArg{nullptr, nullptr, 0, filt_len}; }
+  int host(const double** lo_out, const double** hi_out) const {
+    if (dev) return MIFWT_ERR_UNSUPPORTED;
+    *lo_out = lo;
+    *hi_out = hi;
+    return MIFWT_OK;
+  }
+};
 #ifdef __HIPCC__
 // wave-uniform value in a scalar register (the fused kernels keep their taps in SGPR pairs)
 // (v_readfirstlane through inline assembly: the compiler knows the converted tap is uniform, drops the builtin as redundant and keeps
@@ -168,14 +180,14 @@ template <typename S>
 __device__ __forceinline__ S dtap_hi(const DevTapArg& dt, int m) { return dtap_uniform((S)dt.hi[dt.rev ? dt.len - 1 - m : m]); }
 #endif
 int launch_axis_fwd(int dtype, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis, int64_t n_in,
-                    int mode, int filt_len, const double* lo, const double* hi, hipStream_t stream);
+                    int mode, int filt_len, LevelTaps taps, hipStream_t stream);
 int launch_axis_inv(int dtype, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis, int64_t m_in,
-                    int filt_len, const double* lo, const double* hi, hipStream_t stream);
+                    int filt_len, LevelTaps taps, hipStream_t stream);
 
-// adjoint of one analysis axis pass (g_lo, g_hi -> g_x, halo folded back through the boundary map); lo / hi are
+// adjoint of one analysis axis pass (g_lo, g_hi -> g_x, halo folded back through the boundary map); taps are
 // the DEC taps in PyWavelets order, m_in the coefficient extent, n_sig the signal extent along taxis
 int launch_axis_adj(int dtype, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis, int64_t m_in,
-                    int64_t n_sig, int mode, int filt_len, const double* lo, const double* hi, hipStream_t stream);
+                    int64_t n_sig, int mode, int filt_len, LevelTaps taps, hipStream_t stream);
 
 // ---- streaming single-axis kernels (mifwt_axis_stream.h; any mode, L in the instantiated set) ----------
 // One (input -> low, high) or (low, high -> output) job; up to four jobs of identical geometry per launch.
@@ -197,8 +209,7 @@ struct StreamCall {
   int64_t rows[3];     // inner
   int64_t n_in, n_out;
   int64_t inner;       // outer
-  const double* lo;
-  const double* hi;
+  LevelTaps taps;
   hipStream_t stream;
 };
 
@@ -218,8 +229,8 @@ int dwt2_fwd_stream(const mifwt_level_desc* d, const void* x, void* approx, void
 
 // LDS-tile fused 2-D analysis level (mifwt_dwt2_tile.h): f32 / f16 storage, even L <= 16 and L in {18, 20, 24, 32}
 bool dwt2_fwd_tile_supported(const mifwt_level_desc* d);
-int dwt2_fwd_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details,
-                  const double* dec_lo, const double* dec_hi, hipStream_t stream);
+int dwt2_fwd_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps dec, hipStream_t stream,
+                  BatchSplit split = {0, 0});
 
 // matrix-core (banded-Toeplitz MFMA) fused 2-D analysis level: f16 storage, even L in [18, 32]
 bool dwt2_fwd_mfma_supported(const mifwt_level_desc* d);
@@ -242,8 +253,8 @@ bool dwt2_fwd_roll_supported(const mifwt_level_desc* d1, const mifwt_level_desc*
 // boundary part of the adjoint of an analysis level with a boundary extension (mifwt_adjoint_border.hip): recomputes the samples near
 // the borders of g_x, pad positions folded back, after the zero-mode adjoint (a synthesis launch) has written all of g_x
 bool adjoint_border_supported(const mifwt_level_desc* d);
-int adjoint_border(const mifwt_level_desc* d, const void* g_approx, const void* const* g_details, void* g_x, const double* dec_lo,
-                   const double* dec_hi, hipStream_t stream);
+int adjoint_border(const mifwt_level_desc* d, const void* g_approx, const void* const* g_details, void* g_x, LevelTaps dec,
+                   hipStream_t stream);
 int dwt2_fwd_roll(const mifwt_level_desc* d1, const mifwt_level_desc* d2, const void* x, void* const* details1,
                   void* approx2, void* const* details2, const double* dec_lo, const double* dec_hi, hipStream_t stream);
 
@@ -262,10 +273,10 @@ int dwt2_inv_small(int nlevels, const mifwt_level_desc* const* d, const void* ap
 // (mifwt_dwt2_inv_pyr.hip): f32, even L <= 8; d[0] = the coarsest level
 bool dwt2_inv_pyr_supported(int nlev, const mifwt_level_desc* const* d);
 int dwt2_inv_pyr(int nlev, const mifwt_level_desc* const* d, const void* approx, const void* const* const* details, void* y,
-                 const double* rec_lo, const double* rec_hi, hipStream_t stream);
+                 LevelTaps rec, hipStream_t stream);
 bool dwt2_fwd_pyr_supported(int nlev, const mifwt_level_desc* const* d);
 int dwt2_fwd_pyr(int nlev, const mifwt_level_desc* const* d, const void* x, void* const* const* details, void* approx,
-                  const double* dec_lo, const double* dec_hi, hipStream_t stream);
+                 LevelTaps dec, hipStream_t stream);
 int dwt2_fwd_pyr_schedule(int nlev, const mifwt_level_desc* const* d, uint32_t* wg_start, int capacity);  // the row chunks of the launch
 
 // two consecutive 2-D synthesis levels in one launch (mifwt_idwt2_pair.hip): f32, even L <= 8; d2 = the coarser level
@@ -301,16 +312,16 @@ int idwt1_tail(int dtype, int filt_len, int64_t rows, int64_t m0, int nlevels, c
 
 // which fused 2-D analysis kernel serves this descriptor: kDwt2FwdTile, kDwt2FwdStream, or -1 (neither)
 int dwt2_fwd_choice(const mifwt_level_desc* d);
-int dwt2_fwd_fused(const mifwt_level_desc* d, const void* x, void* approx, void* const* details,
-                   const double* dec_lo, const double* dec_hi, hipStream_t stream);  // runs that choice
+int dwt2_fwd_fused(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps dec,
+                   hipStream_t stream);  // runs that choice
 
 // LDS-tile fused 2-D synthesis level (mifwt_idwt2_tile.h): f32 / f16, even L <= 16 and L in {18, 20, 24, 32}
 bool dwt2_inv_tile_supported(const mifwt_level_desc* d);
-int dwt2_inv_tile(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y,
-                  const double* rec_lo, const double* rec_hi, hipStream_t stream);
+int dwt2_inv_tile(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps rec,
+                  hipStream_t stream);
 int dwt2_inv_choice(const mifwt_level_desc* d);  // kDwt2InvTile, kDwt2InvStream, or -1
-int dwt2_inv_fused(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y,
-                   const double* rec_lo, const double* rec_hi, hipStream_t stream);
+int dwt2_inv_fused(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps rec,
+                   hipStream_t stream);
 
 bool dwt2_inv_stream_supported(const mifwt_level_desc* d);
 int dwt2_inv_stream(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y,
@@ -349,9 +360,9 @@ int plane3_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* con
                const double* hi, void* ws, hipStream_t stream);
 int plane3_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
                const double* hi, void* ws, hipStream_t stream);
-int rows_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-             const double* hi, void* ws, hipStream_t stream);
-int rows_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
-             const double* hi, void* ws, hipStream_t stream);
+int rows_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps taps, void* ws,
+             hipStream_t stream);
+int rows_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps taps, void* ws,
+             hipStream_t stream);
 
 }  // namespace mifwt

@@ -87,13 +87,13 @@ mifwt_level_desc plane_desc(const mifwt_level_desc* d, int64_t depth, bool* fold
 }  // namespace
 
 // ---- LDS-tile fused 2-D analysis: envelope and per-(type, length) instantiation units ---------------------------
-int dwt2_fwd_tile_f32_short(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
-int dwt2_fwd_tile_f16_short(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
-int dwt2_fwd_tile_f64_short(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
-int dwt2_fwd_tile_long18(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
-int dwt2_fwd_tile_long20(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
-int dwt2_fwd_tile_long24(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
-int dwt2_fwd_tile_long32(const mifwt_level_desc*, const void*, void*, void* const*, const double*, const double*, hipStream_t);
+int dwt2_fwd_tile_f32_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_f16_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_f64_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_long18(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_long20(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_long24(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_long32(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
 
 bool dwt2_fwd_tile_supported(const mifwt_level_desc* d) {
   if (d->ndim != 2 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F16 && d->dtype != MIFWT_F64)) return false;
@@ -115,18 +115,18 @@ bool dwt2_fwd_tile_supported(const mifwt_level_desc* d) {
   return true;
 }
 
-int dwt2_fwd_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-                  const double* hi, hipStream_t stream) {
-  if (d->dtype == MIFWT_F64) return dwt2_fwd_tile_f64_short(d, x, approx, details, lo, hi, stream);
+int dwt2_fwd_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps t, hipStream_t stream,
+                  BatchSplit split) {
+  if (d->dtype == MIFWT_F64) return dwt2_fwd_tile_f64_short(d, x, approx, details, t, split, stream);
   switch (d->filt_len) {
-    case 18: return dwt2_fwd_tile_long18(d, x, approx, details, lo, hi, stream);
-    case 20: return dwt2_fwd_tile_long20(d, x, approx, details, lo, hi, stream);
-    case 24: return dwt2_fwd_tile_long24(d, x, approx, details, lo, hi, stream);
-    case 32: return dwt2_fwd_tile_long32(d, x, approx, details, lo, hi, stream);
+    case 18: return dwt2_fwd_tile_long18(d, x, approx, details, t, split, stream);
+    case 20: return dwt2_fwd_tile_long20(d, x, approx, details, t, split, stream);
+    case 24: return dwt2_fwd_tile_long24(d, x, approx, details, t, split, stream);
+    case 32: return dwt2_fwd_tile_long32(d, x, approx, details, t, split, stream);
     default: break;
   }
-  return d->dtype == MIFWT_F16 ? dwt2_fwd_tile_f16_short(d, x, approx, details, lo, hi, stream)
-                               : dwt2_fwd_tile_f32_short(d, x, approx, details, lo, hi, stream);
+  return d->dtype == MIFWT_F16 ? dwt2_fwd_tile_f16_short(d, x, approx, details, t, split, stream)
+                               : dwt2_fwd_tile_f32_short(d, x, approx, details, t, split, stream);
 }
 
 // Two fused 2-D analysis kernels.  Measured on MI355X (64-image batches, 128^2 .. 4096^2 planes): the LDS-tile kernel
@@ -151,28 +151,26 @@ int dwt2_fwd_choice(const mifwt_level_desc* d) {
   return -1;
 }
 
-int dwt2_fwd_fused(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-                   const double* hi, hipStream_t stream) {
-  switch (dwt2_fwd_choice(d)) {
-    case kDwt2FwdTile: return dwt2_fwd_tile(d, x, approx, details, lo, hi, stream);
-    case kDwt2FwdStream:
-      if (g_dtaps.lo) return MIFWT_ERR_UNSUPPORTED;  // (device-resident taps: this kernel takes its taps by value only — never silently on zeros)
-      return dwt2_fwd_stream(d, x, approx, details, lo, hi, stream);
-    case kDwt2FwdPyr: {
-      const mifwt_level_desc* dd[1] = {d};
-      void* const* dp[1] = {details};
-      return dwt2_fwd_pyr(1, dd, x, dp, approx, lo, hi, stream);
-    }
-    default: return MIFWT_ERR_UNSUPPORTED;
+int dwt2_fwd_fused(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps t, hipStream_t stream) {
+  const int kid = dwt2_fwd_choice(d);
+  if (kid == kDwt2FwdTile) return dwt2_fwd_tile(d, x, approx, details, t, stream);
+  if (kid == kDwt2FwdPyr) {
+    const mifwt_level_desc* dd[1] = {d};
+    void* const* dp[1] = {details};
+    return dwt2_fwd_pyr(1, dd, x, dp, approx, t, stream);
   }
+  const double *lo, *hi;  // the streaming kernel takes its taps by value only
+  const int rc = t.host(&lo, &hi);
+  if (rc != MIFWT_OK) return rc;
+  return kid == kDwt2FwdStream ? dwt2_fwd_stream(d, x, approx, details, lo, hi, stream) : MIFWT_ERR_UNSUPPORTED;
 }
 
 // ---- LDS-tile fused 2-D synthesis -------------------------------------------------------------------------------------
-int idwt2_tile_f32_short(const mifwt_level_desc*, const void*, const void* const*, void*, const double*, const double*, hipStream_t);
-int idwt2_tile_f16_short(const mifwt_level_desc*, const void*, const void* const*, void*, const double*, const double*, hipStream_t);
-int idwt2_tile_f64_short(const mifwt_level_desc*, const void*, const void* const*, void*, const double*, const double*, hipStream_t);
-int idwt2_tile_long_a(const mifwt_level_desc*, const void*, const void* const*, void*, const double*, const double*, hipStream_t);
-int idwt2_tile_long_b(const mifwt_level_desc*, const void*, const void* const*, void*, const double*, const double*, hipStream_t);
+int idwt2_tile_f32_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
+int idwt2_tile_f16_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
+int idwt2_tile_f64_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
+int idwt2_tile_long_a(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
+int idwt2_tile_long_b(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
 
 bool dwt2_inv_tile_supported(const mifwt_level_desc* d) {
   if (d->ndim != 2 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F16 && d->dtype != MIFWT_F64)) return false;
@@ -188,13 +186,13 @@ bool dwt2_inv_tile_supported(const mifwt_level_desc* d) {
   return span_a < lim && span_d < lim;
 }
 
-int dwt2_inv_tile(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
-                  const double* hi, hipStream_t stream) {
-  if (d->dtype == MIFWT_F64) return idwt2_tile_f64_short(d, approx, details, y, lo, hi, stream);
-  if (d->filt_len == 18 || d->filt_len == 20) return idwt2_tile_long_a(d, approx, details, y, lo, hi, stream);
-  if (d->filt_len == 24 || d->filt_len == 32) return idwt2_tile_long_b(d, approx, details, y, lo, hi, stream);
-  return d->dtype == MIFWT_F16 ? idwt2_tile_f16_short(d, approx, details, y, lo, hi, stream)
-                               : idwt2_tile_f32_short(d, approx, details, y, lo, hi, stream);
+int dwt2_inv_tile(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps t,
+                  hipStream_t stream) {
+  if (d->dtype == MIFWT_F64) return idwt2_tile_f64_short(d, approx, details, y, t, stream);
+  if (d->filt_len == 18 || d->filt_len == 20) return idwt2_tile_long_a(d, approx, details, y, t, stream);
+  if (d->filt_len == 24 || d->filt_len == 32) return idwt2_tile_long_b(d, approx, details, y, t, stream);
+  return d->dtype == MIFWT_F16 ? idwt2_tile_f16_short(d, approx, details, y, t, stream)
+                               : idwt2_tile_f32_short(d, approx, details, y, t, stream);
 }
 
 int dwt2_inv_choice(const mifwt_level_desc* d) {
@@ -220,23 +218,20 @@ int dwt2_inv_choice(const mifwt_level_desc* d) {
   return -1;
 }
 
-int dwt2_inv_fused(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
-                   const double* hi, hipStream_t stream) {
-  switch (dwt2_inv_choice(d)) {
-    case kDwt2InvTile: return dwt2_inv_tile(d, approx, details, y, lo, hi, stream);
-    case kDwt2InvStream:
-      if (g_dtaps.lo) return MIFWT_ERR_UNSUPPORTED;  // (device-resident taps: these kernels take their taps by value only)
-      return dwt2_inv_stream(d, approx, details, y, lo, hi, stream);
-    case kDwt2InvMfma:
-      if (g_dtaps.lo) return MIFWT_ERR_UNSUPPORTED;
-      return dwt2_inv_mfma(d, approx, details, y, lo, hi, stream);
-    case kDwt2InvPyr: {
-      const mifwt_level_desc* dd[1] = {d};
-      const void* const* dp[1] = {details};
-      return dwt2_inv_pyr(1, dd, approx, dp, y, lo, hi, stream);
-    }
-    default: return MIFWT_ERR_UNSUPPORTED;
+int dwt2_inv_fused(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps t, hipStream_t stream) {
+  const int kid = dwt2_inv_choice(d);
+  if (kid == kDwt2InvTile) return dwt2_inv_tile(d, approx, details, y, t, stream);
+  if (kid == kDwt2InvPyr) {
+    const mifwt_level_desc* dd[1] = {d};
+    const void* const* dp[1] = {details};
+    return dwt2_inv_pyr(1, dd, approx, dp, y, t, stream);
   }
+  const double *lo, *hi;  // the streaming and matrix-core kernels take their taps by value only
+  const int rc = t.host(&lo, &hi);
+  if (rc != MIFWT_OK) return rc;
+  if (kid == kDwt2InvStream) return dwt2_inv_stream(d, approx, details, y, lo, hi, stream);
+  if (kid == kDwt2InvMfma) return dwt2_inv_mfma(d, approx, details, y, lo, hi, stream);
+  return MIFWT_ERR_UNSUPPORTED;
 }
 
 bool rows_route_ok(const mifwt_level_desc* d, int direction) {
@@ -294,6 +289,7 @@ size_t rows_ws_bytes(const mifwt_level_desc* d, int direction) {
 // ---- ndim 3, f32 ----------------------------------------------------------------------------------------
 int plane3_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
                const double* hi, void* ws, hipStream_t stream) {
+  const LevelTaps taps = {lo, hi, false, 0};
   const int64_t D = d->sig_extent[0], plane = d->coef_extent[1] * d->coef_extent[2];
   const int64_t esz = elem_size(d->dtype);
   char* scratch = static_cast<char*>(ws);  // [B, D, 4, Ho, Wo] elements of the level's dtype (byte arithmetic below)
@@ -305,9 +301,7 @@ int plane3_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* con
     // (the input of a deeper level is plane 0 of the previous level's [B, 8, D, H, W] buffer: volumes 8 D H W apart, slices H W apart —
     // one launch per volume cost 32 launches of 5 us each on 32 x 54^3, profiles/r03h_kernel_trace_refshapes.txt)
     void* det[3] = {scratch + plane * esz, scratch + 2 * plane * esz, scratch + 3 * plane * esz};
-    g_batch_split = {D, d->sig_stride[0]};
-    const int rc = dwt2_fwd_tile(&pall, x, scratch, det, lo, hi, stream);
-    g_batch_split = {0, 0};
+    const int rc = dwt2_fwd_tile(&pall, x, scratch, det, taps, stream, {D, d->sig_stride[0]});
     if (rc != MIFWT_OK) return rc;
   } else {
     const int64_t nb = foldable ? 1 : d->batch;
@@ -315,7 +309,7 @@ int plane3_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* con
       const char* xb = static_cast<const char*>(x) + b * d->sig_stride[0] * esz;
       char* sb = scratch + b * D * 4 * plane * esz;
       void* det[3] = {sb + plane * esz, sb + 2 * plane * esz, sb + 3 * plane * esz};
-      const int rc = dwt2_fwd_fused(&p, xb, sb, det, lo, hi, stream);
+      const int rc = dwt2_fwd_fused(&p, xb, sb, det, taps, stream);
       if (rc != MIFWT_OK) return rc;
     }
   }
@@ -341,14 +335,14 @@ int plane3_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* con
   c.n_in = D;
   c.n_out = d->coef_extent[0];
   c.inner = plane;
-  c.lo = lo;
-  c.hi = hi;
+  c.taps = taps;
   c.stream = stream;
   return stream_call(d->dtype, kOuterFwd, c);
 }
 
 int plane3_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
                const double* hi, void* ws, hipStream_t stream) {
+  const LevelTaps taps = {lo, hi, false, 0};
   const int64_t Dout = d->sig_extent[0], plane = d->coef_extent[1] * d->coef_extent[2];
   const int64_t esz = elem_size(d->dtype);
   char* scratch = static_cast<char*>(ws);  // [B, Dout, 4, Ho, Wo] elements of the level's dtype
@@ -373,8 +367,7 @@ int plane3_inv(const mifwt_level_desc* d, const void* approx, const void* const*
   c.n_in = d->coef_extent[0];
   c.n_out = Dout;
   c.inner = plane;
-  c.lo = lo;
-  c.hi = hi;
+  c.taps = taps;
   c.stream = stream;
   int rc = stream_call(d->dtype, kOuterInv, c);
   if (rc != MIFWT_OK) return rc;
@@ -385,15 +378,15 @@ int plane3_inv(const mifwt_level_desc* d, const void* approx, const void* const*
     char* yb = static_cast<char*>(y) + b * d->sig_stride[0] * esz;
     const char* sb = scratch + b * Dout * 4 * plane * esz;
     const void* det[3] = {sb + plane * esz, sb + 2 * plane * esz, sb + 3 * plane * esz};
-    rc = dwt2_inv_fused(&p, sb, det, yb, lo, hi, stream);
+    rc = dwt2_inv_fused(&p, sb, det, yb, taps, stream);
     if (rc != MIFWT_OK) return rc;
   }
   return MIFWT_OK;
 }
 
 // ---- any ndim / dtype: inner-axis pass + one outer-axis pass per further axis ------------------------------
-int rows_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-             const double* hi, void* ws, hipStream_t stream) {
+int rows_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps taps, void* ws,
+             hipStream_t stream) {
   const int nd = d->ndim;
   const int64_t esz = elem_size(d->dtype);
   char* wsp = static_cast<char*>(ws);
@@ -406,8 +399,7 @@ int rows_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const
   memset(&c, 0, sizeof(c));
   c.filt_len = d->filt_len;
   c.mode = d->mode;
-  c.lo = lo;
-  c.hi = hi;
+  c.taps = taps;
   c.stream = stream;
   for (int pass = 0; pass < nd; ++pass) {
     const int a = nd - 1 - pass;        // axis transformed in this pass (innermost first)
@@ -486,8 +478,8 @@ int rows_fwd(const mifwt_level_desc* d, const void* x, void* approx, void* const
   return MIFWT_OK;
 }
 
-int rows_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
-             const double* hi, void* ws, hipStream_t stream) {
+int rows_inv(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps taps, void* ws,
+             hipStream_t stream) {
   const int nd = d->ndim;
   const int64_t esz = elem_size(d->dtype);
   const int nb = 1 << nd;
@@ -501,8 +493,7 @@ int rows_inv(const mifwt_level_desc* d, const void* approx, const void* const* d
   StreamCall c;
   memset(&c, 0, sizeof(c));
   c.filt_len = d->filt_len;
-  c.lo = lo;
-  c.hi = hi;
+  c.taps = taps;
   c.stream = stream;
   int ncur = nb;
   for (int a = 0; a < nd; ++a) {  // outermost axis first: its bit is the most significant of the remaining

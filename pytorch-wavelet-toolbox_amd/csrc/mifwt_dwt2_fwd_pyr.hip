@@ -1366,8 +1366,8 @@ int dwt2_fwd_pyr_schedule(int nlev, const mifwt_level_desc* const* d, uint32_t* 
 }
 
 template <int L, int NLEV>
-static int launch_pyr(const mifwt_level_desc* const* d, const void* x, void* const* const* details, void* approx, const double* lo,
-                       const double* hi, hipStream_t stream) {
+static int launch_pyr(const mifwt_level_desc* const* d, const void* x, void* const* const* details, void* approx, LevelTaps t,
+                      hipStream_t stream) {
   PyrPlan p;
   if (!pyr_plan(NLEV, d, &p)) return MIFWT_ERR_UNSUPPORTED;
   PyrArgs<L, NLEV> a;
@@ -1422,8 +1422,8 @@ static int launch_pyr(const mifwt_level_desc* const* d, const void* x, void* con
   a.hn_div = make_fastdiv((uint32_t)a.H[NLEV]);
   std::copy(p.wg_start, p.wg_start + p.nwg + 1, a.wg_start);
   for (int k = p.nwg + 1; k <= kPyrMaxWG; ++k) a.wg_start[k] = a.wg_start[p.nwg];
-  for (int m = 0; m < L; ++m) a.tap[m] = (f2){(float)lo[m], (float)hi[m]};
-  a.dt = dev_tap_arg(L);
+  for (int m = 0; m < L; ++m) a.tap[m] = (f2){(float)t.tap_lo(m), (float)t.tap_hi(m)};
+  a.dt = t.dev_arg(L);
   const int64_t nwg = (int64_t)p.nwg * p.ngroups;
   // (the per-wave cycle profile of tools/pyr_prof.py exists for the three-level 8-tap kernel only)
   constexpr bool kCanProf = kDiag && L == 8 && NLEV == 3;  // (-DMIFWT_DIAG builds)
@@ -1465,24 +1465,24 @@ static int launch_pyr(const mifwt_level_desc* const* d, const void* x, void* con
 
 template <int L>
 static int launch_pyr_l(int nlev, const mifwt_level_desc* const* d, const void* x, void* const* const* details, void* approx,
-                         const double* lo, const double* hi, hipStream_t stream) {
+                        LevelTaps t, hipStream_t stream) {
   switch (nlev) {
-    case 1: return launch_pyr<L, 1>(d, x, details, approx, lo, hi, stream);
-    case 2: return launch_pyr<L, 2>(d, x, details, approx, lo, hi, stream);
-    case 3: return launch_pyr<L, 3>(d, x, details, approx, lo, hi, stream);
+    case 1: return launch_pyr<L, 1>(d, x, details, approx, t, stream);
+    case 2: return launch_pyr<L, 2>(d, x, details, approx, t, stream);
+    case 3: return launch_pyr<L, 3>(d, x, details, approx, t, stream);
     default: return MIFWT_ERR_UNSUPPORTED;
   }
 }
 
-int dwt2_fwd_pyr(int nlev, const mifwt_level_desc* const* d, const void* x, void* const* const* details, void* approx,
-                  const double* lo, const double* hi, hipStream_t stream) {
+int dwt2_fwd_pyr(int nlev, const mifwt_level_desc* const* d, const void* x, void* const* const* details, void* approx, LevelTaps t,
+                 hipStream_t stream) {
   if (!dwt2_fwd_pyr_supported(nlev, d)) return MIFWT_ERR_UNSUPPORTED;
   switch (d[0]->filt_len) {
-    case 2: return launch_pyr_l<2>(nlev, d, x, details, approx, lo, hi, stream);
-    case 4: return launch_pyr_l<4>(nlev, d, x, details, approx, lo, hi, stream);
-    case 6: return launch_pyr_l<6>(nlev, d, x, details, approx, lo, hi, stream);
-    case 8: return launch_pyr_l<8>(nlev, d, x, details, approx, lo, hi, stream);
-    case 10: return nlev == 1 ? launch_pyr<10, 1>(d, x, details, approx, lo, hi, stream) : MIFWT_ERR_UNSUPPORTED;
+    case 2: return launch_pyr_l<2>(nlev, d, x, details, approx, t, stream);
+    case 4: return launch_pyr_l<4>(nlev, d, x, details, approx, t, stream);
+    case 6: return launch_pyr_l<6>(nlev, d, x, details, approx, t, stream);
+    case 8: return launch_pyr_l<8>(nlev, d, x, details, approx, t, stream);
+    case 10: return nlev == 1 ? launch_pyr<10, 1>(d, x, details, approx, t, stream) : MIFWT_ERR_UNSUPPORTED;
     default: return MIFWT_ERR_UNSUPPORTED;
   }
 }

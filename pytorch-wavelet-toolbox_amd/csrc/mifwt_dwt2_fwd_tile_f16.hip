@@ -4,16 +4,16 @@
 namespace mifwt {
 
 int dwt2_fwd_tile_f16_short(const mifwt_level_desc* d, const void* x, void* approx, void* const* details,
-                            const double* lo, const double* hi, hipStream_t stream) {
+                            LevelTaps t, BatchSplit split, hipStream_t stream) {
   switch (d->filt_len) {
-    case 2: return launch_tr<_Float16, 2>(d, x, approx, details, lo, hi, stream);
-    case 4: return launch_tr<_Float16, 4>(d, x, approx, details, lo, hi, stream);
-    case 6: return launch_tr<_Float16, 6>(d, x, approx, details, lo, hi, stream);
-    case 8: return launch_tr<_Float16, 8>(d, x, approx, details, lo, hi, stream);
-    case 10: return launch_tr<_Float16, 10>(d, x, approx, details, lo, hi, stream);
-    case 12: return launch_tr<_Float16, 12>(d, x, approx, details, lo, hi, stream);
-    case 14: return launch_tr<_Float16, 14>(d, x, approx, details, lo, hi, stream);
-    case 16: return launch_tr<_Float16, 16>(d, x, approx, details, lo, hi, stream);
+    case 2: return launch_tr<_Float16, 2>(d, x, approx, details, t, split, stream);
+    case 4: return launch_tr<_Float16, 4>(d, x, approx, details, t, split, stream);
+    case 6: return launch_tr<_Float16, 6>(d, x, approx, details, t, split, stream);
+    case 8: return launch_tr<_Float16, 8>(d, x, approx, details, t, split, stream);
+    case 10: return launch_tr<_Float16, 10>(d, x, approx, details, t, split, stream);
+    case 12: return launch_tr<_Float16, 12>(d, x, approx, details, t, split, stream);
+    case 14: return launch_tr<_Float16, 14>(d, x, approx, details, t, split, stream);
+    case 16: return launch_tr<_Float16, 16>(d, x, approx, details, t, split, stream);
     default: return MIFWT_ERR_UNSUPPORTED;
   }
 }

@@ -3,10 +3,10 @@
 
 namespace mifwt {
 
-int dwt2_fwd_tile_long20(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-                         const double* hi, hipStream_t stream) {
-  if (d->dtype == MIFWT_F16) return launch_tr<_Float16, 20>(d, x, approx, details, lo, hi, stream);
-  return launch_tr<float, 20>(d, x, approx, details, lo, hi, stream);
+int dwt2_fwd_tile_long20(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps t,
+                         BatchSplit split, hipStream_t stream) {
+  if (d->dtype == MIFWT_F16) return launch_tr<_Float16, 20>(d, x, approx, details, t, split, stream);
+  return launch_tr<float, 20>(d, x, approx, details, t, split, stream);
 }
 
 }  // namespace mifwt

@@ -734,8 +734,8 @@ bool dwt2_inv_pyr_supported(int nlev, const mifwt_level_desc* const* d) {
 }
 
 template <int L, int NLEV>
-static int launch_ipyr(const mifwt_level_desc* const* d, const void* approx, const void* const* const* details, void* y, const double* lo,
-                       const double* hi, hipStream_t stream) {
+static int launch_ipyr(const mifwt_level_desc* const* d, const void* approx, const void* const* const* details, void* y, LevelTaps t,
+                       hipStream_t stream) {
   IPyrPlan p;
   if (!ipyr_plan(NLEV, d, &p)) return MIFWT_ERR_UNSUPPORTED;
   IPyrArgs<L, NLEV> a;
@@ -770,10 +770,10 @@ static int launch_ipyr(const mifwt_level_desc* const* d, const void* approx, con
   a.wu3_off = p.wu3_off;
   a.dbg = g_options[MIFWT_OPT_DEBUG];
   for (int j = 0; j < L / 2; ++j) {
-    a.tlo[j] = (f2){(float)lo[2 * j], (float)lo[2 * j + 1]};
-    a.thi[j] = (f2){(float)hi[2 * j], (float)hi[2 * j + 1]};
+    a.tlo[j] = (f2){(float)t.tap_lo(2 * j), (float)t.tap_lo(2 * j + 1)};
+    a.thi[j] = (f2){(float)t.tap_hi(2 * j), (float)t.tap_hi(2 * j + 1)};
   }
-  a.dt = dev_tap_arg(L);
+  a.dt = t.dev_arg(L);
   const int64_t nwg = d[0]->batch * p.nseg;
   if (nwg > INT32_MAX / 8) return MIFWT_ERR_UNSUPPORTED;
   static DynLdsOnce lds_once;
@@ -793,24 +793,24 @@ static int launch_ipyr(const mifwt_level_desc* const* d, const void* approx, con
 
 template <int L>
 static int launch_ipyr_l(int nlev, const mifwt_level_desc* const* d, const void* approx, const void* const* const* details, void* y,
-                         const double* lo, const double* hi, hipStream_t stream) {
+                         LevelTaps t, hipStream_t stream) {
   switch (nlev) {
-    case 1: return launch_ipyr<L, 1>(d, approx, details, y, lo, hi, stream);
-    case 2: return launch_ipyr<L, 2>(d, approx, details, y, lo, hi, stream);
-    case 3: return launch_ipyr<L, 3>(d, approx, details, y, lo, hi, stream);
+    case 1: return launch_ipyr<L, 1>(d, approx, details, y, t, stream);
+    case 2: return launch_ipyr<L, 2>(d, approx, details, y, t, stream);
+    case 3: return launch_ipyr<L, 3>(d, approx, details, y, t, stream);
     default: return MIFWT_ERR_UNSUPPORTED;
   }
 }
 
 int dwt2_inv_pyr(int nlev, const mifwt_level_desc* const* d, const void* approx, const void* const* const* details, void* y,
-                 const double* lo, const double* hi, hipStream_t stream) {
+                 LevelTaps t, hipStream_t stream) {
   if (!dwt2_inv_pyr_supported(nlev, d)) return MIFWT_ERR_UNSUPPORTED;
   switch (d[0]->filt_len) {
-    case 2: return launch_ipyr_l<2>(nlev, d, approx, details, y, lo, hi, stream);
-    case 4: return launch_ipyr_l<4>(nlev, d, approx, details, y, lo, hi, stream);
-    case 6: return launch_ipyr_l<6>(nlev, d, approx, details, y, lo, hi, stream);
-    case 8: return launch_ipyr_l<8>(nlev, d, approx, details, y, lo, hi, stream);
-    case 10: return launch_ipyr_l<10>(nlev, d, approx, details, y, lo, hi, stream);
+    case 2: return launch_ipyr_l<2>(nlev, d, approx, details, y, t, stream);
+    case 4: return launch_ipyr_l<4>(nlev, d, approx, details, y, t, stream);
+    case 6: return launch_ipyr_l<6>(nlev, d, approx, details, y, t, stream);
+    case 8: return launch_ipyr_l<8>(nlev, d, approx, details, y, t, stream);
+    case 10: return launch_ipyr_l<10>(nlev, d, approx, details, y, t, stream);
     default: return MIFWT_ERR_UNSUPPORTED;
   }
 }

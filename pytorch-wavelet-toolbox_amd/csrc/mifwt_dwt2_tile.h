@@ -221,8 +221,8 @@ __global__ void __launch_bounds__(256, tile_occupancy(L, TR, sizeof(typename Til
 }
 
 template <typename T, int L, int TR>
-int launch_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-                const double* hi, hipStream_t stream) {
+int launch_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps t, BatchSplit split,
+                hipStream_t stream) {
   Dwt2TileArgs<T, L> a;
   a.x = static_cast<const T*>(x);
   a.out[0] = static_cast<T*>(approx);
@@ -231,9 +231,9 @@ int launch_tile(const mifwt_level_desc* d, const void* x, void* approx, void* co
   a.xs_h = d->sig_stride[1];
   a.xs_outer = 0;
   a.div_in.mul = a.div_in.shift = a.div_in.d = 0;
-  if (g_batch_split.inner > 0) {  // (set by the 3-D composed route around this one call: mifwt_compose.hip plane3_fwd)
-    a.div_in = make_fastdiv((uint32_t)g_batch_split.inner);
-    a.xs_outer = g_batch_split.outer_stride;
+  if (split.inner > 0) {  // (the two-level batch of the 3-D composed route: mifwt_compose.hip plane3_fwd)
+    a.div_in = make_fastdiv((uint32_t)split.inner);
+    a.xs_outer = split.outer_stride;
   }
   for (int s = 0; s < 4; ++s) {
     a.os_b[s] = s == 0 ? d->approx_stride[0] : d->detail_stride[0];
@@ -246,8 +246,8 @@ int launch_tile(const mifwt_level_desc* d, const void* x, void* approx, void* co
   a.mode = d->mode;
   a.sync_stage = g_options[MIFWT_OPT_SYNC_STAGE];
   for (int m = 0; m < L; ++m)
-    a.tap[m] = (typename TileArith<T>::vec2){(typename TileArith<T>::type)lo[m], (typename TileArith<T>::type)hi[m]};
-  a.dt = dev_tap_arg(L);
+    a.tap[m] = (typename TileArith<T>::vec2){(typename TileArith<T>::type)t.tap_lo(m), (typename TileArith<T>::type)t.tap_hi(m)};
+  a.dt = t.dev_arg(L);
   a.tiles_c = (a.Wo + kTC - 1) / kTC;
   a.tiles_r = (a.Ho + TR - 1) / TR;
   a.div_c = make_fastdiv((uint32_t)a.tiles_c);
@@ -263,8 +263,8 @@ int launch_tile(const mifwt_level_desc* d, const void* x, void* approx, void* co
 // round costs a full tile latency again), else 12 rows (measured best on 1024^2 / 515^2 planes for L <= 8;
 // taller tiles carry less row halo, which matters for long filters: 16 / 24 rows there).
 template <typename T, int L>
-int launch_tr(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, const double* lo,
-              const double* hi, hipStream_t stream) {
+int launch_tr(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps t, BatchSplit split,
+              hipStream_t stream) {
   int tr = g_options[MIFWT_OPT_TILE_ROWS];
   if (tr <= 0) {
     const int64_t tiles_c = (d->coef_extent[1] + kTC - 1) / kTC;
@@ -281,15 +281,15 @@ int launch_tr(const mifwt_level_desc* d, const void* x, void* approx, void* cons
     }
   }
   if constexpr (L <= 16) {
-    if (tr <= 8) return launch_tile<T, L, 8>(d, x, approx, details, lo, hi, stream);
-    if (tr <= 12) return launch_tile<T, L, 12>(d, x, approx, details, lo, hi, stream);
-    if (tr <= 16) return launch_tile<T, L, 16>(d, x, approx, details, lo, hi, stream);
-    if (tr <= 20) return launch_tile<T, L, 20>(d, x, approx, details, lo, hi, stream);
-    return launch_tile<T, L, 24>(d, x, approx, details, lo, hi, stream);
+    if (tr <= 8) return launch_tile<T, L, 8>(d, x, approx, details, t, split, stream);
+    if (tr <= 12) return launch_tile<T, L, 12>(d, x, approx, details, t, split, stream);
+    if (tr <= 16) return launch_tile<T, L, 16>(d, x, approx, details, t, split, stream);
+    if (tr <= 20) return launch_tile<T, L, 20>(d, x, approx, details, t, split, stream);
+    return launch_tile<T, L, 24>(d, x, approx, details, t, split, stream);
   } else {  // long filters: fewer instantiations
-    if (tr <= 8) return launch_tile<T, L, 8>(d, x, approx, details, lo, hi, stream);
-    if (tr <= 16) return launch_tile<T, L, 16>(d, x, approx, details, lo, hi, stream);
-    return launch_tile<T, L, 24>(d, x, approx, details, lo, hi, stream);
+    if (tr <= 8) return launch_tile<T, L, 8>(d, x, approx, details, t, split, stream);
+    if (tr <= 16) return launch_tile<T, L, 16>(d, x, approx, details, t, split, stream);
+    return launch_tile<T, L, 24>(d, x, approx, details, t, split, stream);
   }
 }
 

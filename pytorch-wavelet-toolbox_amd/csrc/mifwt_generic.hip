@@ -36,9 +36,6 @@ struct AxisJobs {
   AxisJob job[4];
 };
 
-thread_local DeviceTaps g_dtaps = {nullptr, nullptr, 0};
-thread_local int g_dtaps_taken = 0;
-
 // tap m of the pass: from the launch arguments, or (DT) from the device arrays of a filter bank that lives on the GPU
 template <bool DT, typename A>
 __device__ __forceinline__ A tap_of(const A* arg, const double* dev, int rev, int L, int m) {
@@ -184,8 +181,8 @@ __global__ void __launch_bounds__(256) axis_adj_kernel(AxisJobs jobs, AxisGeom g
 
 template <typename T, typename A = T>
 static int launch_axis(int kind, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis,
-                       int64_t n_src, int mode, int filt_len, const double* lo, const double* hi,
-                       hipStream_t stream, int64_t n_sig = 0) {  // kind: 0 analysis, 1 synthesis, 2 analysis adjoint
+                       int64_t n_src, int mode, int filt_len, LevelTaps t, hipStream_t stream,
+                       int64_t n_sig = 0) {  // kind: 0 analysis, 1 synthesis, 2 analysis adjoint
   if (njobs < 1 || njobs > 4 || filt_len < 1 || filt_len > kMaxFilt) return MIFWT_ERR_BADARG;
   AxisJobs js;
   for (int i = 0; i < 4; ++i) js.job[i] = jobs[i < njobs ? i : 0];
@@ -201,16 +198,16 @@ static int launch_axis(int kind, const AxisJob* jobs, int njobs, const int64_t o
   g.n_sig = (int)n_sig;
   g.mode = mode;
   g.filt_len = filt_len;
-  const DeviceTaps dt = g_dtaps;  // (this thread's: set around the call by a mifwt_*_dtaps entry point)
+  const DeviceTaps dt = t.dev_taps();
   Taps<A> taps;
   for (int m = 0; m < kMaxFilt; ++m) {
-    taps.lo[m] = (!dt.lo && m < filt_len) ? (A)lo[m] : A(0);
-    taps.hi[m] = (!dt.lo && m < filt_len) ? (A)hi[m] : A(0);
+    taps.lo[m] = m < filt_len ? (A)t.tap_lo(m) : A(0);
+    taps.hi[m] = m < filt_len ? (A)t.tap_hi(m) : A(0);
   }
   const int64_t want = (g.total + 255) / 256;
   const unsigned gx = (unsigned)(want < 8192 ? want : 8192);  // grid-stride beyond 256 CUs x 32 blocks
   dim3 grid(gx, (unsigned)njobs), block(256);
-  if (dt.lo) {
+  if (t.dev) {
     if (kind == 2)
       hipLaunchKernelGGL((axis_adj_kernel<T, A, true>), grid, block, 0, stream, js, g, taps, dt);
     else if (kind == 1)
@@ -227,26 +224,26 @@ static int launch_axis(int kind, const AxisJob* jobs, int njobs, const int64_t o
 }
 
 int launch_axis_fwd(int dtype, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis, int64_t n_in,
-                    int mode, int filt_len, const double* lo, const double* hi, hipStream_t stream) {
-  if (dtype == MIFWT_F32) return launch_axis<float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, lo, hi, stream);
-  if (dtype == MIFWT_F64) return launch_axis<double>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, lo, hi, stream);
-  if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, lo, hi, stream);
+                    int mode, int filt_len, LevelTaps taps, hipStream_t stream) {
+  if (dtype == MIFWT_F32) return launch_axis<float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
+  if (dtype == MIFWT_F64) return launch_axis<double>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
+  if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
   return MIFWT_ERR_UNSUPPORTED;
 }
 
 int launch_axis_inv(int dtype, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis, int64_t m_in,
-                    int filt_len, const double* lo, const double* hi, hipStream_t stream) {
-  if (dtype == MIFWT_F32) return launch_axis<float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, lo, hi, stream);
-  if (dtype == MIFWT_F64) return launch_axis<double>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, lo, hi, stream);
-  if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, lo, hi, stream);
+                    int filt_len, LevelTaps taps, hipStream_t stream) {
+  if (dtype == MIFWT_F32) return launch_axis<float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
+  if (dtype == MIFWT_F64) return launch_axis<double>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
+  if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
   return MIFWT_ERR_UNSUPPORTED;
 }
 
 int launch_axis_adj(int dtype, const AxisJob* jobs, int njobs, const int64_t out_ext[4], int taxis, int64_t m_in,
-                    int64_t n_sig, int mode, int filt_len, const double* lo, const double* hi, hipStream_t stream) {
-  if (dtype == MIFWT_F32) return launch_axis<float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, lo, hi, stream, n_sig);
-  if (dtype == MIFWT_F64) return launch_axis<double>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, lo, hi, stream, n_sig);
-  if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, lo, hi, stream, n_sig);
+                    int64_t n_sig, int mode, int filt_len, LevelTaps taps, hipStream_t stream) {
+  if (dtype == MIFWT_F32) return launch_axis<float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
+  if (dtype == MIFWT_F64) return launch_axis<double>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
+  if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
   return MIFWT_ERR_UNSUPPORTED;
 }
 

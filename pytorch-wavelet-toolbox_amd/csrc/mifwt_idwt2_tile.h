@@ -169,8 +169,8 @@ __global__ void __launch_bounds__(256, idwt_tile_occupancy(L, TRO, sizeof(typena
 }
 
 template <typename T, int L, int TRO>
-int launch_idwt_tile(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
-                     const double* hi, hipStream_t stream) {
+int launch_idwt_tile(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps t,
+                     hipStream_t stream) {
   constexpr int NQ = 64 - (L / 2 - 1);
   Idwt2TileArgs<T, L> a;
   a.in[0] = static_cast<const T*>(approx);
@@ -188,10 +188,10 @@ int launch_idwt_tile(const mifwt_level_desc* d, const void* approx, const void* 
   a.W = (int)d->sig_extent[1];
   for (int j = 0; j < L / 2; ++j) {
     typedef typename TileArith<T>::type A;
-    a.tlo[j] = (typename TileArith<T>::vec2){(A)lo[2 * j], (A)lo[2 * j + 1]};
-    a.thi[j] = (typename TileArith<T>::vec2){(A)hi[2 * j], (A)hi[2 * j + 1]};
+    a.tlo[j] = (typename TileArith<T>::vec2){(A)t.tap_lo(2 * j), (A)t.tap_lo(2 * j + 1)};
+    a.thi[j] = (typename TileArith<T>::vec2){(A)t.tap_hi(2 * j), (A)t.tap_hi(2 * j + 1)};
   }
-  a.dt = dev_tap_arg(L);
+  a.dt = t.dev_arg(L);
   a.tiles_c = (a.W + 2 * NQ - 1) / (2 * NQ);
   a.tiles_r = (a.H + TRO - 1) / TRO;
   a.div_c = make_fastdiv((uint32_t)a.tiles_c);
@@ -204,8 +204,8 @@ int launch_idwt_tile(const mifwt_level_desc* d, const void* approx, const void* 
 }
 
 template <typename T, int L>
-int launch_idwt_tr(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, const double* lo,
-                   const double* hi, hipStream_t stream) {
+int launch_idwt_tr(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y, LevelTaps t,
+                   hipStream_t stream) {
   constexpr int NQ = 64 - (L / 2 - 1);
   int tro = g_options[MIFWT_OPT_TILE_ROWS];
   if (tro <= 0) {
@@ -221,10 +221,10 @@ int launch_idwt_tr(const mifwt_level_desc* d, const void* approx, const void* co
       }
     }
   }
-  if (tro <= 8) return launch_idwt_tile<T, L, 8>(d, approx, details, y, lo, hi, stream);
-  if (tro <= 16) return launch_idwt_tile<T, L, 16>(d, approx, details, y, lo, hi, stream);
-  if (tro <= 24) return launch_idwt_tile<T, L, 24>(d, approx, details, y, lo, hi, stream);
-  return launch_idwt_tile<T, L, 32>(d, approx, details, y, lo, hi, stream);
+  if (tro <= 8) return launch_idwt_tile<T, L, 8>(d, approx, details, y, t, stream);
+  if (tro <= 16) return launch_idwt_tile<T, L, 16>(d, approx, details, y, t, stream);
+  if (tro <= 24) return launch_idwt_tile<T, L, 24>(d, approx, details, y, t, stream);
+  return launch_idwt_tile<T, L, 32>(d, approx, details, y, t, stream);
 }
 
 }  // namespace mifwt

@@ -4,16 +4,16 @@
 namespace mifwt {
 
 int idwt2_tile_f16_short(const mifwt_level_desc* d, const void* approx, const void* const* details, void* y,
-                         const double* lo, const double* hi, hipStream_t stream) {
+                         LevelTaps t, hipStream_t stream) {
   switch (d->filt_len) {
-    case 2: return launch_idwt_tr<_Float16, 2>(d, approx, details, y, lo, hi, stream);
-    case 4: return launch_idwt_tr<_Float16, 4>(d, approx, details, y, lo, hi, stream);
-    case 6: return launch_idwt_tr<_Float16, 6>(d, approx, details, y, lo, hi, stream);
-    case 8: return launch_idwt_tr<_Float16, 8>(d, approx, details, y, lo, hi, stream);
-    case 10: return launch_idwt_tr<_Float16, 10>(d, approx, details, y, lo, hi, stream);
-    case 12: return launch_idwt_tr<_Float16, 12>(d, approx, details, y, lo, hi, stream);
-    case 14: return launch_idwt_tr<_Float16, 14>(d, approx, details, y, lo, hi, stream);
-    case 16: return launch_idwt_tr<_Float16, 16>(d, approx, details, y, lo, hi, stream);
+    case 2: return launch_idwt_tr<_Float16, 2>(d, approx, details, y, t, stream);
+    case 4: return launch_idwt_tr<_Float16, 4>(d, approx, details, y, t, stream);
+    case 6: return launch_idwt_tr<_Float16, 6>(d, approx, details, y, t, stream);
+    case 8: return launch_idwt_tr<_Float16, 8>(d, approx, details, y, t, stream);
+    case 10: return launch_idwt_tr<_Float16, 10>(d, approx, details, y, t, stream);
+    case 12: return launch_idwt_tr<_Float16, 12>(d, approx, details, y, t, stream);
+    case 14: return launch_idwt_tr<_Float16, 14>(d, approx, details, y, t, stream);
+    case 16: return launch_idwt_tr<_Float16, 16>(d, approx, details, y, t, stream);
     default: return MIFWT_ERR_UNSUPPORTED;
   }
 }

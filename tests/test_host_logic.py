@@ -271,6 +271,93 @@ def test_cabi_descriptor_validation_and_dispatch():
     assert lib.mifwt_dwt_fwd(ctypes.byref(d), None, None, None, None, None, None, 0, None) == -1
 
 
+def _default_layout_desc(ndim, dtype_id, mode_id, flen, batch, sig):
+    """A dense level in the layout of ``_engine.kernel_id``: valid for analysis and synthesis alike (coef = (n + L - 1) // 2)."""
+    d = _engine.LevelDesc()
+    d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, dtype_id, mode_id, flen, batch
+    coef = [(n + flen - 1) // 2 for n in sig]
+    s = c = 1
+    for a in reversed(range(ndim)):
+        d.sig_extent[a], d.coef_extent[a] = sig[a], coef[a]
+        d.sig_stride[1 + a] = s
+        d.approx_stride[1 + a] = d.detail_stride[1 + a] = c
+        s, c = s * sig[a], c * coef[a]
+    d.sig_stride[0] = s
+    d.approx_stride[0] = d.detail_stride[0] = c << ndim
+    return d
+
+
+def test_cabi_device_tap_routes_follow_the_host_routes():
+    """A device-tap call runs on the kernel of the host-tap call where that kernel reads device taps (ids 3 / 4 / 7 / 8 / 16 / 22), on
+    the generic passes everywhere else, and its workspace is that of the kernel it runs on — for every direction."""
+    lib = _engine.load_library()
+    ref = ctypes.byref
+    extents = {1: [(37,), (4096,), (1 << 20,)], 2: [(40, 40), (515, 515), (1024, 1024), (2048, 2048)],
+               3: [(16, 16, 16), (64, 64, 64), (129, 129, 129), (256, 256, 256)]}
+    descs = [_default_layout_desc(ndim, dt, mode, flen, batch, sig)
+             for ndim in (1, 2, 3) for dt in (0, 1, 2) for mode in range(5) for flen in (2, 4, 8, 10, 16, 20, 22, 32)
+             for batch in (1, 8) for sig in extents[ndim]]
+    rows = [(d, direction, lib.mifwt_kernel_id(ref(d), direction), lib.mifwt_kernel_id_dtaps(ref(d), direction),
+             lib.mifwt_workspace_bytes(ref(d), direction), lib.mifwt_workspace_bytes_dtaps(ref(d), direction))
+            for d in descs for direction in range(4)]
+    _engine.set_option(_engine.OPT_FORCE_GENERIC, 1)
+    try:
+        generic = [lib.mifwt_workspace_bytes(ref(d), direction) for d, direction, *_ in rows]
+    finally:
+        _engine.set_option(_engine.OPT_FORCE_GENERIC, 0)
+    reads_device_taps = {3, 4, 7, 8, 16, 22}
+    seen = set()
+    for (d, direction, kid, kid_dev, ws, ws_dev), ws_generic in zip(rows, generic):
+        where = (d.ndim, d.dtype, d.mode, d.filt_len, d.batch, tuple(d.sig_extent[:d.ndim]), direction)
+        assert kid_dev == (kid if kid < 0 or kid in reads_device_taps else 0), where
+        assert ws_dev == (ws if kid_dev == kid else ws_generic), where
+        seen.add(kid_dev)
+    assert {0, 3, 4, 7, 8, 16, 22} <= seen  # (the grid reaches every kernel that reads device taps)
+    assert lib.mifwt_kernel_id_dtaps(ref(descs[0]), 4) == -1 and lib.mifwt_workspace_bytes_dtaps(ref(descs[0]), 4) == 0
+
+
+def test_cabi_level_entry_points_early_exits_host_and_device_taps():
+    """The early exits of the eight level entry points and of the two outer-axis ones return before any launch (no GPU needed), with
+    the same codes for host and device taps."""
+    lib = _engine.load_library()
+    ref, vp = ctypes.byref, ctypes.c_void_p
+    OK, BADARG, UNSUPPORTED, WORKSPACE = 0, -1, -2, -3
+    taps = (ctypes.c_double * 32)(*range(1, 33))
+    dev = vp(ctypes.addressof(taps))  # (device taps are never read on the host: any non-null pointer)
+    buf = vp(4096)
+    planes = (vp * 7)(*[buf] * 7)
+    # entry point, its taps, whether the band planes come before the single array (x / y / g_x / g_y = the first or the last pointer)
+    calls = [(lib.mifwt_dwt_fwd, taps, False), (lib.mifwt_dwt_inv, taps, True), (lib.mifwt_dwt_fwd_adjoint, taps, True),
+             (lib.mifwt_dwt_inv_adjoint, taps, False), (lib.mifwt_dwt_fwd_dtaps, dev, False), (lib.mifwt_dwt_inv_dtaps, dev, True),
+             (lib.mifwt_dwt_fwd_adjoint_dtaps, dev, True), (lib.mifwt_dwt_inv_adjoint_dtaps, dev, False)]
+    for mode in (_engine.MODE_IDS["reflect"], _engine.MODE_IDS["zero"]):
+        for fn, t, bands_first in calls:
+            def call(d, first=buf, ws=None, ws_bytes=0):
+                return fn(ref(d), first, *((planes, buf) if bands_first else (buf, planes)), t, t, ws, ws_bytes, None)
+
+            where = (fn.__name__, mode)
+            d = _default_layout_desc(2, 0, mode, 8, 4, (64, 64))
+            assert call(d, first=None) == BADARG, where
+            d.batch = 0
+            assert call(d) == OK, where
+            d = _default_layout_desc(2, 0, mode, 22, 4, (512, 512))  # generic passes: they need scratch
+            assert call(d) == WORKSPACE and call(d, ws=buf, ws_bytes=1) == WORKSPACE, where
+    for host, device in ((taps, None), (None, dev)):
+        def fwd(x=buf, flen=8, batch=4, h=host, dp=device):
+            m = (64 + flen - 1) // 2
+            return lib.mifwt_dwt1_fwd_outer(0, batch, 64, 16, x, 64 * 16, 16, buf, buf, m * 16, 16, _engine.MODE_IDS["reflect"], flen,
+                                            h, h, dp, dp, None)
+
+        def inv(y=buf, flen=8, batch=4, h=host, dp=device):
+            m = (64 + flen - 1) // 2
+            return lib.mifwt_dwt1_inv_outer(0, batch, m, 64, 16, buf, m * 16, 16, buf, m * 16, 16, y, 64 * 16, 16, flen, h, h, dp, dp, None)
+
+        for f, data in ((fwd, "x"), (inv, "y")):
+            assert f(**{data: None}) == BADARG and f(h=None, dp=None) == BADARG, (f.__name__, device)
+            assert f(flen=22) == UNSUPPORTED, (f.__name__, device)
+            assert f(batch=0) == OK, (f.__name__, device)
+
+
 # ---- multi-level entry points: envelopes and argument checks run on the host ----------------------------------------------
 def _dense_desc(dtype_id, mode, flen, batch, sig, coef):
     d = _engine.LevelDesc()
