@@ -285,6 +285,14 @@ class DevTaps:
         return self.t.data_ptr()
 
 
+def outer_axis_supported(flen: int, dtype: torch.dtype) -> bool:
+    """Whether the outer-axis level kernels (C ABI ``mifwt_dwt1_fwd_outer`` / ``mifwt_dwt1_inv_outer``) serve this filter length and
+    storage type: float32 / float64 and the lengths of the streaming axis kernels, even L up to 20, 24 and 32 (``stream_filter_supported``
+    in csrc/mifwt_compose.hip); they answer every other request with MIFWT_ERR_UNSUPPORTED.  The natural-layout tap gradients of a 2-D
+    level need them (_fwt._analysis_tap_grads / _synthesis_tap_grads)."""
+    return dtype in (torch.float32, torch.float64) and ((2 <= flen <= 20 and flen % 2 == 0) or flen in (24, 32))
+
+
 def _is_dev(taps) -> bool:
     return isinstance(taps, DevTaps)
 

@@ -51,11 +51,12 @@ def _analysis_tap_grads(x, g_buf, dec_lo, dec_hi, mode_id):
     g_lo = torch.zeros(flen, dtype=torch.float64, device=x.device)
     g_hi = torch.zeros_like(g_lo)
     eng = _engine.ENGINE
-    if nd == 2 and flen <= 32 and hasattr(eng, "tap_correlate_planes"):
+    if nd == 2 and _engine.outer_axis_supported(flen, x.dtype) and hasattr(eng, "tap_correlate_planes"):
         # Two axes, every operand in its NATURAL layout (round 6: the transposed copies in front of the row reductions were a third of
         # a training step).  Along the rows axis H: z = the level along W of every row (inner-axis kernel), reduced along H by the
         # column kernel; along W: z = the level along H (outer-axis kernel on its own), reduced along W by the row kernel.  The band
-        # planes of g_buf are strided views, taken as they are.
+        # planes of g_buf are strided views, taken as they are.  Only where the outer-axis kernels serve the bank (length and type); every
+        # other bank takes the per-axis loop below.
         B, H, W = x.shape
         xc = x if x.stride(-1) == 1 else x.contiguous()
         rows = xc.reshape(B * H, W)  # (a view of a dense input; a copy of a plane of a level buffer: the deeper levels, a quarter each)
@@ -97,7 +98,7 @@ def _synthesis_tap_grads(g_y, approx, details, rec_lo, rec_hi):
     g_hi = torch.zeros_like(g_lo)
     eng = _engine.ENGINE
     bands = [approx] + list(details)
-    if nd == 2 and flen <= 32 and hasattr(eng, "synthesis_outer"):
+    if nd == 2 and _engine.outer_axis_supported(flen, g_y.dtype) and hasattr(eng, "synthesis_outer"):
         # two axes, every operand in its natural layout (see _analysis_tap_grads).  Along H: u = the two bands with letter sigma along H
         # synthesised along W (inner-axis kernel, rows (b, k_h)), reduced along H by the column kernel; along W: u = the two bands with
         # letter sigma along W synthesised along H (outer-axis kernel), reduced along W by the row kernel.

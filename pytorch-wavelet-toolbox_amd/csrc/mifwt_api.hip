@@ -355,6 +355,17 @@ static int validate_call(const mifwt_level_desc* desc, int direction) {
   return validate(&z, 0);
 }
 
+// Whether the adjoint of an analysis level is a synthesis level of the same extents: the synthesis covers [0, 2 M - L + 2 - t) with
+// t in {0, 1}, which holds for every even filter length; an odd filter on an even extent leaves the reference's pads one coefficient
+// short of that (M = (N + L - 3) / 2: 2 M - L + 2 = N - 1), and such an adjoint takes the generic passes.
+static bool adjoint_is_synthesis(const mifwt_level_desc* d) {
+  for (int a = 0; a < d->ndim; ++a) {
+    const int64_t full = 2 * d->coef_extent[a] - d->filt_len + 2;
+    if (d->sig_extent[a] != full && d->sig_extent[a] != full - 1) return false;
+  }
+  return true;
+}
+
 // Which kernel serves a (validated) level call; direction 2 / 3 = adjoint of the analysis / synthesis level described by desc.  A
 // zero-mode analysis adjoint IS a synthesis level (reversed dec taps) and every synthesis adjoint IS a zero-mode analysis level
 // (reversed rec taps), so they ride on the fast kernels; other boundary modes take the synthesis launch plus the border kernel where
@@ -362,7 +373,7 @@ static int validate_call(const mifwt_level_desc* desc, int direction) {
 static int route(const mifwt_level_desc* desc, int direction, bool dev) {
   int kid;
   if (direction == 2) {
-    kid = desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc) ? pick_kernel(desc, 1) : kGeneric;
+    kid = (desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc)) && adjoint_is_synthesis(desc) ? pick_kernel(desc, 1) : kGeneric;
   } else if (direction == 3) {
     const mifwt_level_desc z = as_zero_mode(desc);
     kid = pick_kernel(&z, 0);
@@ -483,7 +494,8 @@ static int level_fwd_adjoint(const mifwt_level_desc* desc, const void* g_approx,
   // exactly [0, N).  A boundary extension: the interior of the adjoint is the zero-mode adjoint (a sample away from the borders has no
   // pad position mapped onto it); the samples near a border are recomputed with the pad positions folded back (mifwt_adjoint_border.hip).
   // Device taps take that route only where its synthesis kernel reads them.
-  const bool synth = dec.dev ? route(desc, 2, true) != kGeneric : desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc);
+  const bool synth = dec.dev ? route(desc, 2, true) != kGeneric
+                             : adjoint_is_synthesis(desc) && (desc->mode == MIFWT_MODE_ZERO || adjoint_border_supported(desc));
   if (!synth) {
     const size_t need = generic_ws(desc, 1);
     if (need > 0 && (!workspace || workspace_bytes < need)) return MIFWT_ERR_WORKSPACE;

@@ -358,6 +358,105 @@ def test_cabi_level_entry_points_early_exits_host_and_device_taps():
             assert f(batch=0) == OK, (f.__name__, device)
 
 
+def test_2d_tap_gradients_leave_the_outer_axis_kernels_to_the_lengths_they_serve(oracle_engine, monkeypatch):
+    """the natural-layout tap gradients of a 2-D level were taken for every bank of at most 32 taps, and the
+    outer-axis kernels answer 22 - 30 taps and odd lengths with "no kernel for".  With stand-ins that refuse what the C entry points
+    refuse, learnable wavedec2 / waverec2 banks of those lengths (random, four independent filters) give the differentiable reference's
+    gradients, and the lengths the kernels serve still take the natural-layout route."""
+    from oracle import torch_autograd_ref as R
+
+    eng = _engine.ENGINE
+    served = []
+
+    def refusing(name, taps_at):
+        inner = getattr(eng, name)
+
+        def call(*args):
+            if not _engine.outer_axis_supported(len(args[taps_at]), args[0].dtype):
+                raise RuntimeError("libmifwt: valid request this build has no kernel for (code -2)")
+            served.append(len(args[taps_at]))
+            return inner(*args)
+        return call
+
+    monkeypatch.setattr(eng, "analysis_outer", refusing("analysis_outer", 1))
+    monkeypatch.setattr(eng, "synthesis_outer", refusing("synthesis_outer", 2))
+
+    def weight(t, i):
+        return torch.cos(0.37 * torch.arange(t.numel(), dtype=torch.float64) + i).reshape(t.shape)
+
+    for flen, mode in ((22, "symmetric"), (26, "zero"), (5, "reflect"), (20, "periodic")):
+        rng = np.random.default_rng(flen)
+        bank = [rng.standard_normal(flen) for _ in range(4)]
+        x = torch.from_numpy(rng.standard_normal((2, 2 * flen + 7, 2 * flen + 3)))
+        grads = []
+        for mod in (ptwt_amd, R):
+            taps = [torch.tensor(b, requires_grad=True) for b in bank]
+            coeffs = mod.wavedec2(x, tuple(taps), mode=mode, level=1)
+            y = mod.waverec2(coeffs, tuple(taps))
+            loss = sum((weight(t, i) * t).sum() for i, (_, t) in enumerate(G.flatten_coeffs(coeffs))) + (weight(y, 7) * y).sum()
+            grads.append(torch.autograd.grad(loss, taps))
+        for a, b in zip(*grads):
+            assert G.relerr(a.numpy(), b.numpy()) < 1e-11, (flen, mode)
+    assert served and set(served) == {20}
+
+
+def test_analysis_adjoint_runs_as_a_synthesis_level_only_where_the_extents_fit():
+    """The adjoint of an analysis level rides on the synthesis kernels only where it IS a synthesis level of the same extents,
+    N in {2 M - L + 2, 2 M - L + 1}: every even filter length, an odd one on odd extents.  An odd filter on an even extent (the
+    reference's pads give M = (N + L - 3) / 2) takes the generic passes, with host and with device taps; a zero-mode backward there
+    failed with "bad argument" when it was sent to the synthesis kernels."""
+    lib = _engine.load_library()
+    ref = ctypes.byref
+    for ndim, dtype_id, mode in ((1, 1, "zero"), (1, 0, "zero"), (2, 1, "zero"), (2, 0, "zero"), (2, 0, "reflect")):
+        for flen in range(2, 34):
+            for n in range(2 * flen + 10, 2 * flen + 14):
+                sig = (n,) * ndim
+                d = _engine.LevelDesc()
+                d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, dtype_id, _engine.MODE_IDS[mode], flen, 2
+                m = (n + n % 2 + flen - 2) // 2
+                s = c = 1
+                for a in reversed(range(ndim)):
+                    d.sig_extent[a], d.coef_extent[a] = n, m
+                    d.sig_stride[1 + a] = s
+                    d.approx_stride[1 + a] = d.detail_stride[1 + a] = c
+                    s, c = s * n, c * m
+                d.sig_stride[0] = s
+                d.approx_stride[0] = d.detail_stride[0] = c << ndim
+                fits = n in (2 * m - flen + 2, 2 * m - flen + 1)
+                assert fits == (flen % 2 == 0 or n % 2 == 1), (flen, n)
+                where = (ndim, dtype_id, mode, flen, sig)
+                if not fits:
+                    assert lib.mifwt_kernel_id(ref(d), 2) == 0 and lib.mifwt_kernel_id_dtaps(ref(d), 2) == 0, where
+                elif mode == "zero" and flen % 2 == 0 and flen <= 20:
+                    assert lib.mifwt_kernel_id(ref(d), 2) != 0, where  # (the synthesis kernels, as before)
+
+
+def test_outer_axis_predicate_matches_the_c_entry_points():
+    """``_engine.outer_axis_supported`` (which 2-D tap gradients take the natural-layout route) answers exactly what the two outer-axis
+    entry points accept: OK, not UNSUPPORTED, for an empty batch — every filter length 1..128, every storage type, host and device
+    taps — so the Python gate and the library's ``stream_filter_supported`` cannot drift apart."""
+    lib = _engine.load_library()
+    vp = ctypes.c_void_p
+    OK, UNSUPPORTED = 0, -2
+    taps = (ctypes.c_double * 32)(*range(1, 33))
+    dev = vp(ctypes.addressof(taps))
+    buf = vp(4096)
+    accepted = []
+    for dtype, dtype_id in _engine._DTYPE_IDS.items():
+        for flen in range(1, 129):
+            m = (64 + flen - 1) // 2
+            want = _engine.outer_axis_supported(flen, dtype)
+            for h, dp in ((taps, None), (None, dev)):
+                rc_f = lib.mifwt_dwt1_fwd_outer(dtype_id, 0, 64, 16, buf, 64 * 16, 16, buf, buf, m * 16, 16, _engine.MODE_IDS["reflect"], flen,
+                                                h, h, dp, dp, None)
+                rc_i = lib.mifwt_dwt1_inv_outer(dtype_id, 0, m, 64, 16, buf, m * 16, 16, buf, m * 16, 16, buf, 64 * 16, 16, flen, h, h, dp, dp,
+                                                None)
+                assert rc_f == rc_i == (OK if want else UNSUPPORTED), (dtype, flen, dp is not None, rc_f, rc_i)
+            if want:
+                accepted.append((dtype_id, flen))
+    assert accepted == [(d, L) for d in (0, 1) for L in (2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 24, 32)]
+
+
 # ---- multi-level entry points: envelopes and argument checks run on the host ----------------------------------------------
 def _dense_desc(dtype_id, mode, flen, batch, sig, coef):
     d = _engine.LevelDesc()
