@@ -318,6 +318,52 @@ int mifwt_swt_inv(int dtype, int filt_len, int64_t rows, int64_t n, int64_t dila
                   int64_t a_row_stride, int64_t d_row_stride, void* y, int64_t y_row_stride, const double* rec_lo,
                   const double* rec_hi, double scale, void* stream);
 
+/* BOUNDARY-WAVELET levels — the padding-free transforms ptwt.MatrixWavedec / MatrixWaverec (src/ptwt/matmul_transform.py:409-430: pad one
+ * sample if odd + torch.sparse.mm(A, x) + split; :679-703: cat + torch.sparse.mm(S, c) + drop the pad sample) and, in their separable
+ * form, MatrixWavedec2 / MatrixWaverec2 (src/ptwt/matmul_transform_2.py:514-529: A_rows X A_cols^T through two transposes + splits;
+ * :799-840: the cats, S_rows C S_cols^T, crops).  The N x N level matrix (N = 2 M) is never formed: row m of a band is
+ *     y[m] = sum_t f[t] x[2 m + L/2 - t]                                   (f = lo / hi below, zero extension never reached)
+ * except for the first n_top = ceil((L-2)/4) and the last n_bot = floor(L/4) rows of each band, whose orthogonalised coefficients come from
+ * a table: one fused launch per level (kernel ids 26 / 27: f32 / f64, even L <= 20, 1 or 2 transformed axes, unit innermost strides, every
+ * axis at least 2 (L-1) samples so that the two ends do not overlap).
+ *   desc      as for mifwt_dwt_fwd, with sig_extent the REAL extent (may be odd) and coef_extent = ceil(sig_extent / 2) per axis; an odd
+ *             extent has one virtual sample at its end whose value `mode` defines (the reference's odd_coeff_padding_mode).  Synthesis
+ *             accepts sig_extent in {2 M, 2 M - 1} and computes only those samples; it ignores `mode`.
+ *   lo / hi   HOST taps, PyWavelets order: dec_lo / dec_hi for mifwt_bwt_fwd, rec_lo / rec_hi for mifwt_bwt_inv (which reverses them: the
+ *             rows of S^T are built from the reversed filters, matmul_transform.py:111-118)
+ *   tables    boundary rows of the same bank on the DEVICE, float64 [2 bands][max(n_top + n_bot, 1)][L]: rows 0 .. n_top-1 hold the top
+ *             rows over columns 0 .. L-1 (last entry 0), the others the bottom rows over columns N-L .. N-1 (first entry 0).  They do not
+ *             depend on N, so one table serves every level and every axis; the kernels read it once per workgroup that owns an end.
+ * mifwt_bwt_fwd applies the rows of the bank (lo, hi, tables), mifwt_bwt_inv the TRANSPOSED bank of (reversed lo, reversed hi, tables).
+ * Adjoints therefore need no entry points of their own: the adjoint of an analysis level is mifwt_bwt_inv with (reversed dec_lo, reversed
+ * dec_hi, the ANALYSIS tables), the adjoint of a synthesis level mifwt_bwt_fwd with (reversed rec_lo, reversed rec_hi, the SYNTHESIS
+ * tables) and mode zero — for biorthogonal filters S != A^T, so an adjoint never borrows the other direction's tables.  (The gradient of
+ * the virtual sample of an odd extent is folded back by the caller: run the adjoint over 2 M samples, add column 2 M - 1 to its source.)
+ * mifwt_bwt_supported / mifwt_bwt_kernel_id are decided on the host: 1 / the kernel id where the fused kernels serve the level, 0 /
+ * MIFWT_ERR_UNSUPPORTED where they do not (the calls then launch nothing), MIFWT_ERR_BADARG for inconsistent extents.
+ * mifwt_bwt_axis_fwd / _inv: ONE axis of a level through a run-time tap loop (ids 28 / 29): arrays [outer, n, inner] with (outer, axis,
+ * inner) strides in elements, even L <= MIFWT_MAX_FILT, f32 / f64, n (real extent, may be odd) with 2 ceil(n/2) >= 2 (L-1). */
+#define MIFWT_KID_BWT_FWD 26
+#define MIFWT_KID_BWT_INV 27
+#define MIFWT_KID_BWT_AXIS_FWD 28
+#define MIFWT_KID_BWT_AXIS_INV 29
+typedef struct mifwt_bwt_tables {
+  const double* rows; /* DEVICE pointer, layout above */
+  int32_t n_top, n_bot;
+} mifwt_bwt_tables;
+int mifwt_bwt_supported(const mifwt_level_desc* desc, int direction);
+int mifwt_bwt_kernel_id(const mifwt_level_desc* desc, int direction);
+int mifwt_bwt_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* lo, const double* hi,
+                  const mifwt_bwt_tables* tables, void* stream);
+int mifwt_bwt_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* lo, const double* hi,
+                  const mifwt_bwt_tables* tables, void* stream);
+int mifwt_bwt_axis_fwd(int dtype, int filt_len, int mode, int64_t outer, int64_t n, int64_t inner, const void* x, const int64_t* x_strides,
+                       void* lo_out, const int64_t* lo_strides, void* hi_out, const int64_t* hi_strides, const double* lo, const double* hi,
+                       const mifwt_bwt_tables* tables, void* stream);
+int mifwt_bwt_axis_inv(int dtype, int filt_len, int64_t outer, int64_t n, int64_t inner, const void* lo_in, const int64_t* lo_strides,
+                       const void* hi_in, const int64_t* hi_strides, void* y, const int64_t* y_strides, const double* lo, const double* hi,
+                       const mifwt_bwt_tables* tables, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -369,7 +415,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          mifwt_dwt1_inv_long; likewise)
  *   20 / 21  every level of a 2-D analysis / synthesis of a small plane in one launch (mifwt_dwt2_fwd_pyramid's second kernel /
  *          mifwt_dwt2_inv_pyramid; likewise)
- *   22     up to three fused 2-D synthesis levels of a big plane per launch (mifwt_dwt2_inv_pyramid's second kernel; likewise) */
+ *   22     up to three fused 2-D synthesis levels of a big plane per launch (mifwt_dwt2_inv_pyramid's second kernel; likewise)
+ *   26 / 27  fused boundary-wavelet analysis / synthesis level, 1-D and 2-D (mifwt_bwt_fwd / mifwt_bwt_inv; answered by mifwt_bwt_kernel_id)
+ *   28 / 29  one axis of a boundary-wavelet level through a run-time tap loop (mifwt_bwt_axis_fwd / mifwt_bwt_axis_inv) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

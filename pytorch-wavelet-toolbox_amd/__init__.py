@@ -25,6 +25,8 @@ from .conv_transform_2 import wavedec2, waverec2
 from .conv_transform_3 import wavedec3, waverec3
 from .packets import WaveletPacket, WaveletPacket2D
 from .stationary_transform import iswt, swt
+from .matmul_transform import MatrixWavedec, MatrixWaverec
+from .matmul_transform_2 import MatrixWavedec2, MatrixWaverec2
 from .separable_conv_transform import fswavedec2, fswavedec3, fswaverec2, fswaverec3
 from .graphs import CapturedCall, capture
 from ._wavelets import set_device_taps
@@ -56,6 +58,10 @@ __all__ = [
     "swt",
     "iswt",
     "WaveletPacket2D",
+    "MatrixWavedec",
+    "MatrixWaverec",
+    "MatrixWavedec2",
+    "MatrixWaverec2",
     "capture",
     "CapturedCall",
 ]

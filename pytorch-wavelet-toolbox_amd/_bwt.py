@@ -1,0 +1,359 @@
+"""Host path of the boundary-wavelet levels (C ABI ``mifwt_bwt_*``, include/mifwt.h; kernels csrc/mifwt_bwt.hip).
+
+A *bank* is what one direction of the transform applies: the two row filters ``f`` of ``_boundary.py`` and the boundary tables
+built from them.  Two level maps exist,
+
+    rows(bank, mode)        x [B, n..]              -> buffer [B, 2^d, M..]   c = B x          (analysis; adjoint of synthesis)
+    transposed(bank, n..)   bands [B, M..] each     -> y [B, n..]             y = B^T c        (synthesis; adjoint of analysis)
+
+each one fused launch per level (kernel ids 26 / 27) for float32 / float64, even ``L <= 20`` and axes of at least ``2 (L-1)``
+samples; longer filters run one generic launch per axis (28 / 29); a level with an axis shorter than ``2 (L-1)`` — a few dozen
+samples — is a dense ``torch.matmul`` with the small level matrix.  The tables are cached per bank and uploaded once per device;
+after that a call allocates its outputs and enqueues launches, nothing else: no host round trip, capturable.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _boundary, _engine
+
+KID_FWD, KID_INV, KID_AXIS_FWD, KID_AXIS_INV = 26, 27, 28, 29
+_ZERO = _engine.MODE_IDS["zero"]
+
+
+class BwtTables(ctypes.Structure):
+    """Mirror of ``mifwt_bwt_tables``."""
+
+    _fields_ = [("rows", ctypes.c_void_p), ("n_top", ctypes.c_int32), ("n_bot", ctypes.c_int32)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    lib = _engine.load_library()
+    if not _bound:
+        vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+        dbl_p, desc_p, tab_p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_engine.LevelDesc), ctypes.POINTER(BwtTables)
+        i64_p, vpp = ctypes.POINTER(i64), ctypes.POINTER(vp)
+        for name in ("mifwt_bwt_supported", "mifwt_bwt_kernel_id"):
+            getattr(lib, name).restype = ci
+            getattr(lib, name).argtypes = [desc_p, ci]
+        lib.mifwt_bwt_fwd.restype = ci
+        lib.mifwt_bwt_fwd.argtypes = [desc_p, vp, vp, vpp, dbl_p, dbl_p, tab_p, vp]
+        lib.mifwt_bwt_inv.restype = ci
+        lib.mifwt_bwt_inv.argtypes = [desc_p, vp, vpp, vp, dbl_p, dbl_p, tab_p, vp]
+        lib.mifwt_bwt_axis_fwd.restype = ci
+        lib.mifwt_bwt_axis_fwd.argtypes = [ci, ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
+        lib.mifwt_bwt_axis_inv.restype = ci
+        lib.mifwt_bwt_axis_inv.argtypes = [ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
+        _bound = True
+    return lib
+
+
+class Bank:
+    """Row filters + boundary tables of one direction ("analysis" / "synthesis") of a filter bank; device copies are made once per
+    device and kept."""
+
+    def __init__(self, taps: Tuple[Tuple[float, ...], ...], method: str, which: str):
+        self.taps, self.method, self.which = taps, method, which
+        f_lo, f_hi = _boundary.row_filters(taps, which)
+        self.filt_len = len(f_lo)
+        self.f_lo, self.f_hi = tuple(float(v) for v in f_lo), tuple(float(v) for v in f_hi)
+        self.r_lo, self.r_hi = self.f_lo[::-1], self.f_hi[::-1]
+        self.n_top, self.n_bot = _boundary.boundary_rows(self.filt_len)
+        self._host_tab = _boundary.kernel_tables(taps, method, which)
+        self._dev: Dict[torch.device, Tuple[torch.Tensor, BwtTables]] = {}
+        self._dense: dict = {}
+
+    def tables(self, device: torch.device) -> BwtTables:
+        hit = self._dev.get(device)
+        if hit is None:
+            t = torch.from_numpy(np.ascontiguousarray(self._host_tab)).to(device)
+            hit = self._dev[device] = (t, BwtTables(t.data_ptr(), self.n_top, self.n_bot))
+        return hit[1]
+
+    def dense(self, n: int, device: torch.device, dtype: torch.dtype) -> torch.Tensor:
+        """The rows of this bank for an even length ``n`` as a dense [n, n] matrix on the device (short levels)."""
+        key = (n, device, dtype)
+        m = self._dense.get(key)
+        if m is None:
+            a = _boundary.level_matrix(self.taps, n, self.method, self.which)
+            a = a if self.which == "analysis" else a.T
+            m = self._dense[key] = torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)
+        return m
+
+
+_banks: dict = {}
+
+
+def bank(taps, method: str, which: str) -> Bank:
+    key = (taps, which)  # (both methods give the same tables, _boundary.py)
+    b = _banks.get(key)
+    if b is None:
+        if len(_banks) > 256:
+            _banks.clear()
+        b = _banks[key] = Bank(taps, method, which)
+    return b
+
+
+def virtual_source(n: int, mode_id: int) -> int:
+    """Index of the sample the virtual sample of an odd extent copies (-1: it is zero) — one sample of the reference's _fwt_pad."""
+    return {0: -1, 1: n - 1, 2: n - 2, 3: 0, 4: n - 1}[mode_id]
+
+
+def is_short(extents: Sequence[int], flen: int) -> bool:
+    return any(n + (n & 1) < 2 * (flen - 1) for n in extents)
+
+
+_plans: dict = {}
+_engine._routing_caches.append(_plans)
+
+
+def _desc(ndim, dtype, mode_id, flen, batch, sig, sig_stride, coef, a_stride, d_stride):
+    d = _engine.LevelDesc()
+    d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _engine._DTYPE_IDS[dtype], mode_id, flen, batch
+    for a in range(ndim):
+        d.sig_extent[a], d.coef_extent[a] = sig[a], coef[a]
+    for a in range(ndim + 1):
+        d.sig_stride[a], d.approx_stride[a], d.detail_stride[a] = sig_stride[a], a_stride[a], d_stride[a]
+    return d
+
+
+def _launch(direction: int, kid: int, extent, anchor: torch.Tensor, call) -> None:
+    dev = anchor.device
+    with torch.cuda.device(dev):
+        if _engine.level_events is None:
+            rc = call(_engine._raw_stream(dev.index if dev.index is not None else torch.cuda.current_device()))
+        else:
+            stream = torch.cuda.current_stream(dev)
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record(stream)
+            rc = call(stream.cuda_stream)
+            ev[1].record(stream)
+            _engine.level_events.append((("bwt_fwd", "bwt_inv")[direction], kid, tuple(extent), ev[0], ev[1]))
+    if rc != 0:
+        _engine._check(rc)
+
+
+def _unit_last(t: torch.Tensor) -> torch.Tensor:
+    return t if t.stride(-1) == 1 or t.shape[-1] == 1 and t.is_contiguous() else t.contiguous()
+
+
+def _strides3(t: torch.Tensor):
+    return _engine._arr(ctypes.c_int64, 3)(*t.stride())
+
+
+# ---- the two level maps (no autograd) ---------------------------------------------------------------------------------------------
+def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
+    """x [B, n0(, n1)] -> buffer [B, 2^d, M0(, M1)], plane s = band s (bit (d-1-a) of s set <=> high-pass along axis a)."""
+    _engine._require_gpu(x)
+    ndim = x.dim() - 1
+    sig = [int(n) for n in x.shape[1:]]
+    coef = [(n + 1) // 2 for n in sig]
+    L = bk.filt_len
+    if is_short(sig, L):
+        return _rows_dense(x, bk, mode_id)
+    x = _unit_last(x)
+    buf = torch.empty((x.shape[0], 1 << ndim, *coef), dtype=x.dtype, device=x.device)
+    if buf.numel() == 0:
+        return buf
+    lib = _lib()
+    key = (0, x.shape, x.stride(), x.dtype, mode_id, L)
+    p = _plans.get(key)
+    if p is None:
+        bs = list(buf.stride())
+        st = [bs[0]] + bs[2:]
+        d = _desc(ndim, x.dtype, mode_id, L, x.shape[0], sig, x.stride(), coef, st, st)
+        kid = lib.mifwt_bwt_kernel_id(ctypes.byref(d), 0)
+        if kid < 0 and kid != -2:
+            _engine._check(kid)
+        p = _plans[key] = (d, ctypes.byref(d), kid, bs[1] * x.element_size())
+    d, ref, kid, plane = p
+    tab = bk.tables(x.device)
+    lo, hi = _engine._taps_array(bk.f_lo), _engine._taps_array(bk.f_hi)
+    if kid == KID_FWD:
+        base, xp = buf.data_ptr(), x.data_ptr()
+        ptrs = _engine._band_ptrs(base, plane, (1 << ndim) - 1)
+        _launch(0, kid, sig, x, lambda stream: lib.mifwt_bwt_fwd(ref, xp, base, ptrs, lo, hi, ctypes.byref(tab), stream))
+        return buf
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"Input dtype {x.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
+    dt = _engine._DTYPE_IDS[x.dtype]
+
+    def axis_fwd(src, n, outer, inner, out_lo, out_hi, mode):
+        _launch(0, KID_AXIS_FWD, (n,), src, lambda stream: lib.mifwt_bwt_axis_fwd(
+            dt, L, mode, outer, n, inner, src.data_ptr(), _strides3(src), out_lo.data_ptr(), _strides3(out_lo), out_hi.data_ptr(),
+            _strides3(out_hi), lo, hi, ctypes.byref(tab), stream))
+
+    if ndim == 1:
+        axis_fwd(x.unsqueeze(-1), sig[0], x.shape[0], 1, buf[:, 0].unsqueeze(-1), buf[:, 1].unsqueeze(-1), mode_id)
+    elif ndim == 2:
+        x = x.contiguous()
+        b, n0, n1 = x.shape
+        tmp = torch.empty((2, b, n0, coef[1]), dtype=x.dtype, device=x.device)
+        axis_fwd(x.reshape(b * n0, n1, 1), n1, b * n0, 1, tmp[0].reshape(b * n0, coef[1], 1), tmp[1].reshape(b * n0, coef[1], 1), mode_id)
+        axis_fwd(tmp[0], n0, b, coef[1], buf[:, 0], buf[:, 2], mode_id)
+        axis_fwd(tmp[1], n0, b, coef[1], buf[:, 1], buf[:, 3], mode_id)
+    else:
+        raise NotImplementedError("boundary-wavelet levels exist for one and two transformed axes")
+    return buf
+
+
+def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequence[int]) -> torch.Tensor:
+    """bands (2^d tensors [B, M0(, M1)], band order as above) -> y [B, n0(, n1)], n in {2 M, 2 M - 1} per axis."""
+    a0 = bands[0]
+    _engine._require_gpu(a0)
+    ndim = a0.dim() - 1
+    coef = [int(m) for m in a0.shape[1:]]
+    sig = [int(n) for n in out_extent]
+    L = bk.filt_len
+    if is_short(sig, L):
+        return _transposed_dense(bands, bk, sig)
+    bands = [_unit_last(t) for t in bands]
+    if len({t.stride() for t in bands[1:]}) > 1:
+        bands = [bands[0]] + [t.contiguous() for t in bands[1:]]
+    y = torch.empty((a0.shape[0], *sig), dtype=a0.dtype, device=a0.device)
+    if y.numel() == 0:
+        return y
+    lib = _lib()
+    key = (1, a0.shape, tuple(sig), bands[0].stride(), bands[1].stride(), a0.dtype, L)
+    p = _plans.get(key)
+    if p is None:
+        d = _desc(ndim, a0.dtype, _ZERO, L, a0.shape[0], sig, y.stride(), coef, bands[0].stride(), bands[1].stride())
+        kid = lib.mifwt_bwt_kernel_id(ctypes.byref(d), 1)
+        if kid < 0 and kid != -2:
+            _engine._check(kid)
+        p = _plans[key] = (d, ctypes.byref(d), kid, 0)
+    d, ref, kid, _ = p
+    tab = bk.tables(a0.device)
+    if kid == KID_INV:
+        # (the C entry takes the filters in rec order and reverses them into row filters)
+        lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
+        ptrs = _engine._arr(ctypes.c_void_p, len(bands) - 1)(*[t.data_ptr() for t in bands[1:]])
+        ap, yp = bands[0].data_ptr(), y.data_ptr()
+        _launch(1, kid, sig, a0, lambda stream: lib.mifwt_bwt_inv(ref, ap, ptrs, yp, lo, hi, ctypes.byref(tab), stream))
+        return y
+    if a0.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"Input dtype {a0.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
+    dt = _engine._DTYPE_IDS[a0.dtype]
+    lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
+
+    def axis_inv(c_lo, c_hi, n, outer, inner, out):
+        _launch(1, KID_AXIS_INV, (n,), c_lo, lambda stream: lib.mifwt_bwt_axis_inv(
+            dt, L, outer, n, inner, c_lo.data_ptr(), _strides3(c_lo), c_hi.data_ptr(), _strides3(c_hi), out.data_ptr(), _strides3(out),
+            lo, hi, ctypes.byref(tab), stream))
+
+    if ndim == 1:
+        axis_inv(bands[0].unsqueeze(-1), bands[1].unsqueeze(-1), sig[0], a0.shape[0], 1, y.unsqueeze(-1))
+    elif ndim == 2:
+        b = a0.shape[0]
+        tmp = torch.empty((2, b, sig[0], coef[1]), dtype=a0.dtype, device=a0.device)
+        axis_inv(bands[0], bands[2], sig[0], b, coef[1], tmp[0])
+        axis_inv(bands[1], bands[3], sig[0], b, coef[1], tmp[1])
+        axis_inv(tmp[0].reshape(b * sig[0], coef[1], 1), tmp[1].reshape(b * sig[0], coef[1], 1), sig[1], b * sig[0], 1,
+                 y.reshape(b * sig[0], sig[1], 1))
+    else:
+        raise NotImplementedError("boundary-wavelet levels exist for one and two transformed axes")
+    return y
+
+
+# ---- short levels: dense matrices, plain torch (differentiable as it stands, no host synchronisation) ----------------------------
+def _with_virtual(x: torch.Tensor, dim: int, mode_id: int) -> torch.Tensor:
+    n = x.shape[dim]
+    if n % 2 == 0:
+        return x
+    src = virtual_source(n, mode_id)
+    extra = x.narrow(dim, src, 1) if src >= 0 else torch.zeros_like(x.narrow(dim, 0, 1))
+    return torch.cat([x, extra], dim)
+
+
+def _rows_dense(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
+    ndim = x.dim() - 1
+    for a in range(ndim):
+        x = _with_virtual(x, 1 + a, mode_id)
+    if ndim == 1:
+        c = x @ bk.dense(x.shape[1], x.device, x.dtype).T
+        return c.reshape(x.shape[0], 2, -1)
+    m_r = bk.dense(x.shape[1], x.device, x.dtype)
+    m_c = bk.dense(x.shape[2], x.device, x.dtype)
+    c = m_r @ x @ m_c.T
+    h, w = c.shape[1] // 2, c.shape[2] // 2
+    return c.reshape(x.shape[0], 2, h, 2, w).permute(0, 1, 3, 2, 4).reshape(x.shape[0], 4, h, w)
+
+
+def _transposed_dense(bands: Sequence[torch.Tensor], bk: Bank, sig: Sequence[int]) -> torch.Tensor:
+    a0 = bands[0]
+    ndim = a0.dim() - 1
+    if ndim == 1:
+        c = torch.cat([bands[0], bands[1]], -1)
+        y = c @ bk.dense(c.shape[-1], a0.device, a0.dtype)
+        return y[:, : sig[0]]
+    c = torch.cat([torch.cat([bands[0], bands[1]], -1), torch.cat([bands[2], bands[3]], -1)], -2)
+    y = bk.dense(c.shape[1], a0.device, a0.dtype).T @ c @ bk.dense(c.shape[2], a0.device, a0.dtype)
+    return y[:, : sig[0], : sig[1]]
+
+
+# ---- autograd: each map's backward is the other map with the same bank ---------------------------------------------------------------
+def _fold_virtual(t: torch.Tensor, dim: int, n: int, src: int) -> torch.Tensor:
+    """Gradient of appending the virtual sample along ``dim``: drop entry n, add it onto entry ``src``."""
+    if t.shape[dim] == n:
+        return t
+    main = t.narrow(dim, 0, n)
+    if src < 0:
+        return main
+    parts = [main.narrow(dim, 0, src), main.narrow(dim, src, 1) + t.narrow(dim, n, 1), main.narrow(dim, src + 1, n - src - 1)]
+    return torch.cat(parts, dim)
+
+
+class _Rows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bk, mode_id):
+        ctx.meta = (bk, mode_id, tuple(x.shape[1:]))
+        return rows_level(x, bk, mode_id)
+
+    @staticmethod
+    def backward(ctx, g):
+        bk, mode_id, sig = ctx.meta
+        full = [n + (n & 1) for n in sig]
+        g_x = _Transposed.apply(bk, tuple(full), *[g[:, s] for s in range(g.shape[1])])
+        for a, n in enumerate(sig):
+            g_x = _fold_virtual(g_x, 1 + a, n, virtual_source(n, mode_id))
+        return g_x, None, None
+
+
+class _Transposed(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bk, out_extent, *bands):
+        ctx.bk = bk
+        return transposed_level(bands, bk, out_extent)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        g = _Rows.apply(g_y, ctx.bk, _ZERO)
+        return (None, None, *[g[:, s] for s in range(g.shape[1])])
+
+
+def rows(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
+    if is_short(x.shape[1:], bk.filt_len) or not (torch.is_grad_enabled() and x.requires_grad):
+        return rows_level(x, bk, mode_id)
+    return _Rows.apply(x, bk, mode_id)
+
+
+def transposed(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequence[int]) -> torch.Tensor:
+    if is_short(out_extent, bk.filt_len) or not (torch.is_grad_enabled() and any(t.requires_grad for t in bands)):
+        return transposed_level(bands, bk, out_extent)
+    return _Transposed.apply(bk, tuple(out_extent), *bands)
+
+
+# ---- the level matrices as sparse tensors (sparse_fwt_operator / sparse_ifwt_operator) ------------------------------------------------
+def sparse_level(bk: Bank, n: int, device, dtype) -> torch.Tensor:
+    """Rows of the bank for an even length ``n`` as a torch sparse COO matrix [n, n] (assembled on the host from the tables)."""
+    r, c, v = _boundary.level_coo(bk.taps, n, bk.method, bk.which)  # (analysis: A;  synthesis: S, already transposed)
+    t = torch.sparse_coo_tensor(np.stack([r, c]), v, size=(n, n), dtype=torch.float64)
+    return t.to(device=device, dtype=dtype).coalesce()

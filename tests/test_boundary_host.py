@@ -1,0 +1,260 @@
+"""Host-side tests of the boundary-wavelet transforms (no GPU): the boundary tables against the reference's matrices
+(tests/golden/ptwt_ref_boundary.npz, group "blocks"), the public interface and its errors, and the host half of the C ABI."""
+import ctypes
+import inspect
+import io
+import contextlib
+
+import numpy as np
+import pytest
+import torch
+
+import ptwt_amd
+from ptwt_amd import _boundary, _bwt, _engine
+from ptwt_amd._wavelets import host_taps
+from tests import _golden as G
+
+WAVELETS = ("haar", "db2", "db3", "db4", "sym5", "db8", "db10", "coif2", "bior2.2")
+
+
+def test_tables_match_the_reference_blocks():
+    """gramschmidt: exact in sign; qr: up to one sign per row.  1e-12 on entries (the reference's two methods differ from one another
+    by at most 4e-14 for L <= 20)."""
+    z, idx = G.load("ptwt_ref_boundary.npz")
+    blocks = [c for c in idx if c["group"] == "blocks"]
+    assert {c["wavelet"] for c in blocks} == set(WAVELETS) and {c["method"] for c in blocks} == {"qr", "gramschmidt"}
+    flipped = 0
+    for case in blocks:
+        taps = host_taps(case["wavelet"])
+        nt, nb = _boundary.boundary_rows(case["filt_len"])
+        for which in ("analysis", "synthesis"):
+            got = _boundary.boundary_blocks(taps, case["method"], which)
+            for band in ("lo", "hi"):
+                for end, rows in (("top", nt), ("bot", nb)):
+                    want = z["%s_%s_%s_%s" % (case["key"], which, band, end)]
+                    mine = got["%s_%s" % (band, end)]
+                    assert mine.shape == want.shape == (rows, case["filt_len"] - 1)
+                    if case["method"] == "qr":
+                        s = np.sign((mine * want).sum(axis=1))
+                        flipped += int((s < 0).sum())
+                        mine = mine * s[:, None]
+                    assert np.abs(mine - want).max(initial=0.0) < 1e-12, (case, which, band, end)
+    assert flipped > 0  # (the reference's qr signs do differ from the Gram-Schmidt signs somewhere: the rule above is exercised)
+
+
+@pytest.mark.parametrize("wavelet", ["db12", "db16", "db20"])
+def test_long_filters_are_orthogonal_to_1e_9(wavelet):
+    """No golden for L > 20: the reference's classical Gram-Schmidt has lost orthogonality there (1e-12 at L = 24, 6e-5 at L = 40, which
+    would fail this bound); its QR reaches 1.5e-11 at L = 40."""
+    taps = host_taps(wavelet)
+    L = len(taps[0])
+    for n in (2 * (L - 1), 4 * L + 2):
+        a = _boundary.level_matrix(taps, n, "qr", "analysis")
+        assert np.abs(a @ a.T - np.eye(n)).max() < 1e-9
+        s = _boundary.level_matrix(taps, n, "gramschmidt", "synthesis")
+        assert np.abs(s @ a - np.eye(n)).max() < 1e-9
+
+
+def test_blocks_do_not_depend_on_the_length_and_short_levels_are_orthogonal():
+    for wavelet in WAVELETS:
+        taps = host_taps(wavelet)
+        L = len(taps[0])
+        nt, nb = _boundary.boundary_rows(L)
+        blocks = _boundary.boundary_blocks(taps, "qr", "analysis")
+        assert blocks is _boundary.boundary_blocks(taps, "gramschmidt", "analysis")  # cached per bank, both methods
+        for n in (2 * (L - 1), 2 * (L - 1) + 2, 6 * L, 6 * L + 2):
+            if n < 2:
+                continue
+            a = _boundary.level_matrix(taps, n, "qr", "analysis")
+            h = n // 2
+            for off, band in ((0, "lo"), (h, "hi")):
+                assert np.array_equal(a[off:off + nt, : L - 1], blocks[band + "_top"])
+                assert np.array_equal(a[off + h - nb:off + h, n - L + 1:], blocks[band + "_bot"])
+                assert not a[off:off + nt, L - 1:].any() and not a[off + h - nb:off + h, : n - L + 1].any()
+        if not wavelet.startswith("bior"):
+            for n in range(L + (L % 2), 2 * (L - 1), 2):  # L <= N < 2 (L - 1): the two ends overlap
+                a = _boundary.level_matrix(taps, n, "qr", "analysis")
+                assert np.abs(a @ a.T - np.eye(n)).max() < 1e-12, (wavelet, n)
+        tab = _boundary.kernel_tables(taps, "qr", "analysis")
+        assert tab.shape == (2, max(nt + nb, 1), L) and not tab[:, :nt, L - 1].any() and not tab[:, nt:nt + nb, 0].any()
+
+
+def test_exports_signatures_and_defaults():
+    for name in ("MatrixWavedec", "MatrixWaverec", "MatrixWavedec2", "MatrixWaverec2"):
+        assert name in ptwt_amd.__all__ and hasattr(ptwt_amd, name)
+    from ptwt_amd import matmul_transform, matmul_transform_2
+
+    assert matmul_transform.MatrixWavedec is ptwt_amd.MatrixWavedec and matmul_transform_2.MatrixWaverec2 is ptwt_amd.MatrixWaverec2
+
+    def params(cls):
+        return {k: (v.kind, v.default) for k, v in inspect.signature(cls.__init__).parameters.items() if k != "self"}
+
+    P, K = inspect.Parameter.POSITIONAL_OR_KEYWORD, inspect.Parameter.KEYWORD_ONLY
+    assert params(ptwt_amd.MatrixWavedec) == {"wavelet": (P, inspect.Parameter.empty), "level": (P, None), "axis": (K, None),
+                                              "orthogonalization": (K, "qr"), "odd_coeff_padding_mode": (K, "zero")}
+    assert params(ptwt_amd.MatrixWaverec) == {"wavelet": (P, inspect.Parameter.empty), "axis": (K, None), "orthogonalization": (K, "qr")}
+    assert params(ptwt_amd.MatrixWavedec2) == {"wavelet": (P, inspect.Parameter.empty), "level": (P, None), "axes": (K, None),
+                                               "orthogonalization": (K, "qr"), "separable": (K, True),
+                                               "odd_coeff_padding_mode": (K, "zero")}
+    assert params(ptwt_amd.MatrixWaverec2) == {"wavelet": (P, inspect.Parameter.empty), "axes": (K, None), "orthogonalization": (K, "qr"),
+                                               "separable": (K, True)}
+    dec = ptwt_amd.MatrixWavedec("db2", 3)
+    assert (dec.level, dec.input_length, dec.padded, dec.size_list, dec.pad_list, dec.axis) == (3, None, False, [], [], -1)
+    dec2 = ptwt_amd.MatrixWavedec2("db2")
+    assert (dec2.level, dec2.padded, dec2.size_list, dec2.pad_list, dec2.axes, dec2.separable) == (None, False, [], [], (-2, -1), True)
+    rec = ptwt_amd.MatrixWaverec("db2")
+    assert (rec.level, rec.input_length, rec.padded) == (None, None, False)
+
+
+def test_errors_come_before_any_gpu_work():
+    for cls in (ptwt_amd.MatrixWavedec, ptwt_amd.MatrixWaverec, ptwt_amd.MatrixWavedec2, ptwt_amd.MatrixWaverec2):
+        with pytest.raises(NotImplementedError):
+            cls("db2", orthogonalization="householder")
+        with pytest.raises(ValueError, match="same length"):
+            cls((torch.ones(4), torch.ones(4), torch.ones(6), torch.ones(6)))
+        with pytest.warns(DeprecationWarning):
+            obj = cls("db2", boundary="gramschmidt")
+        assert obj.orthogonalization == "gramschmidt"
+        with pytest.raises(TypeError):
+            cls("db2", boundary="qr", orthogonalization="qr")
+    for cls in (ptwt_amd.MatrixWavedec2, ptwt_amd.MatrixWaverec2):
+        with pytest.raises(NotImplementedError, match="Kronecker"):
+            cls("db2", separable=False)
+    with pytest.raises(NotImplementedError):
+        ptwt_amd.MatrixWavedec2("db2").sparse_fwt_operator
+    with pytest.raises(NotImplementedError):
+        ptwt_amd.MatrixWaverec2("db2").sparse_ifwt_operator
+    with pytest.raises(ValueError, match="Call this object first"):
+        ptwt_amd.MatrixWavedec("db2").sparse_fwt_operator
+    with pytest.raises(ValueError, match="Call this object first"):
+        ptwt_amd.MatrixWaverec("db2").sparse_ifwt_operator
+    x1, x2 = torch.randn(3, 64), torch.randn(3, 32, 32)
+    for level in (0, -2):
+        with pytest.raises(ValueError, match="positive integer"):
+            ptwt_amd.MatrixWavedec("db2", level)(x1)
+        with pytest.raises(ValueError, match="positive integer"):
+            ptwt_amd.MatrixWavedec2("db2", level)(x2)
+    with pytest.raises(ValueError, match="same shape"):
+        ptwt_amd.MatrixWaverec("db2")([torch.randn(3, 8), torch.randn(3, 9)])
+    with pytest.raises(ValueError, match="same shape"):
+        ptwt_amd.MatrixWaverec2("db2")((torch.randn(3, 8, 8), ptwt_amd.WaveletDetailTuple2d(*(torch.randn(3, 8, 9) for _ in range(3)))))
+    with pytest.raises(ValueError, match="3-tuple"):
+        ptwt_amd.MatrixWaverec2("db2")((torch.randn(3, 8, 8), torch.randn(3, 8, 8)))
+    with pytest.raises(ValueError, match="Padding mode not supported"):
+        ptwt_amd.MatrixWavedec("db2", 1, odd_coeff_padding_mode="antireflect")(torch.randn(3, 33))
+    # a CPU tensor: the package's usual refusal, after the argument checks
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        ptwt_amd.MatrixWavedec("db2", 2)(x1)
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        ptwt_amd.MatrixWavedec2("db2", 2)(x2)
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        ptwt_amd.MatrixWaverec("db2")([torch.randn(3, 8), torch.randn(3, 8)])
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        ptwt_amd.MatrixWaverec2("db2")((torch.randn(3, 8, 8), ptwt_amd.WaveletDetailTuple2d(*(torch.randn(3, 8, 8) for _ in range(3)))))
+    with pytest.raises(ValueError):
+        ptwt_amd.MatrixWavedec("db2", 1)(torch.randn(2, 64).half())
+    # the packet trees still refuse the boundary mode
+    with pytest.raises(NotImplementedError):
+        ptwt_amd.WaveletPacket(torch.randn(2, 64), "db2", mode="boundary")
+
+
+def test_level_bookkeeping_and_the_too_deep_warning():
+    """level=None is int(log2(N / (L - 1))); a level whose input is shorter than L is not computed (stderr warning)."""
+    dec = ptwt_amd.MatrixWavedec("db4", 5)
+    err = io.StringIO()
+    with contextlib.redirect_stderr(err), pytest.raises(RuntimeError, match="ROCm device"):
+        dec(torch.randn(2, 40))
+    assert "too large" in err.getvalue() and "level 3" in err.getvalue()
+    assert dec.size_list == [40, 20, 10, 5] and dec.pad_list == [False, False, False] and not dec.padded and dec.input_length == 40
+    dec = ptwt_amd.MatrixWavedec("db3", None)
+    with pytest.raises(RuntimeError):
+        dec(torch.randn(97))
+    assert dec.level == int(np.log2(98 / 5)) == 4 and dec.input_length == 98
+    assert dec.size_list == [98, 50, 26, 14, 7] and dec.pad_list == [False, True, True, True] and dec.padded
+    dec2 = ptwt_amd.MatrixWavedec2("db2", None)
+    with pytest.raises(RuntimeError):
+        dec2(torch.randn(33, 47))
+    assert dec2.level == 3 and dec2.size_list == [(34, 48), (18, 24), (10, 12), (5, 6)]
+    assert dec2.pad_list == [(True, True), (False, True), (False, True)] and dec2.padded
+
+
+def _desc(ndim, dtype, flen, batch, sig, mode=0, coef=None, inner=1):
+    d = _engine.LevelDesc()
+    d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, dtype, mode, flen, batch
+    coef = coef or [(n + 1) // 2 for n in sig]
+    s, c = inner, inner
+    for a in reversed(range(ndim)):
+        d.sig_extent[a], d.coef_extent[a] = sig[a], coef[a]
+        d.sig_stride[1 + a], d.approx_stride[1 + a], d.detail_stride[1 + a] = s, c, c
+        s, c = s * sig[a], c * coef[a]
+    d.sig_stride[0], d.approx_stride[0], d.detail_stride[0] = s, c * (1 << ndim), c * (1 << ndim)
+    return d
+
+
+def test_c_abi_host_side():
+    lib = _bwt._lib()
+    for sym in ("mifwt_bwt_fwd", "mifwt_bwt_inv", "mifwt_bwt_supported", "mifwt_bwt_kernel_id", "mifwt_bwt_axis_fwd", "mifwt_bwt_axis_inv"):
+        assert hasattr(lib, sym)
+    assert lib.mifwt_abi_version() == 3 == _engine.ABI_VERSION
+    F32, F64, F16 = 0, 1, 2
+    OK, BADARG, UNSUPPORTED = 0, -1, -2
+
+    def kid(d, direction):
+        return lib.mifwt_bwt_kernel_id(ctypes.byref(d), direction), lib.mifwt_bwt_supported(ctypes.byref(d), direction)
+
+    for dtype in (F32, F64):
+        for L in range(2, 22, 2):
+            assert kid(_desc(1, dtype, L, 7, [4096]), 0) == (26, 1)
+            assert kid(_desc(1, dtype, L, 7, [4095]), 1) == (27, 1)
+            assert kid(_desc(2, dtype, L, 3, [101, 64], mode=4), 0) == (26, 1)
+            assert kid(_desc(2, dtype, L, 3, [64, 77]), 1) == (27, 1)
+    assert kid(_desc(1, F32, 8, 2, [14]), 0) == (26, 1)                     # N = 2 (L - 1): the shortest axis with disjoint ends
+    assert kid(_desc(1, F32, 8, 2, [12]), 0) == (UNSUPPORTED, 0)            # L <= N < 2 (L - 1): the dense route of the host layer
+    assert kid(_desc(2, F64, 8, 2, [12, 64]), 1) == (UNSUPPORTED, 0)
+    assert kid(_desc(1, F32, 22, 2, [4096]), 0) == (UNSUPPORTED, 0)         # long filters: the per-axis passes
+    assert kid(_desc(1, F32, 32, 2, [4096]), 1) == (UNSUPPORTED, 0)
+    assert kid(_desc(1, F16, 8, 2, [4096]), 0) == (UNSUPPORTED, 0)
+    assert kid(_desc(3, F32, 4, 2, [32, 32, 32]), 0) == (UNSUPPORTED, 0)
+    assert kid(_desc(1, F32, 8, 2, [4096], inner=2), 0) == (UNSUPPORTED, 0)  # non-unit innermost stride
+    # inconsistent requests
+    assert kid(_desc(1, F32, 8, 2, [4096], coef=[2051]), 0) == (BADARG, BADARG)  # the padded transform's extent, not ceil(N / 2)
+    assert kid(_desc(1, F32, 8, 2, [4096], coef=[2047]), 1) == (BADARG, BADARG)
+    assert kid(_desc(2, F32, 8, 2, [64, 63], coef=[32, 31]), 0) == (BADARG, BADARG)
+    assert kid(_desc(1, F32, 7, 2, [4096]), 0) == (BADARG, BADARG)
+    assert kid(_desc(1, F32, 8, 2, [6]), 0) == (BADARG, BADARG)              # shorter than the filter
+    assert kid(_desc(1, 5, 8, 2, [4096]), 0) == (BADARG, BADARG)
+    assert kid(_desc(1, F32, 8, 2, [4096], mode=9), 0) == (BADARG, BADARG)
+    assert lib.mifwt_bwt_kernel_id(ctypes.byref(_desc(1, F32, 8, 2, [4096])), 2) == BADARG
+    assert lib.mifwt_bwt_kernel_id(None, 0) == BADARG
+    # the calls refuse before they launch: null pointers, inconsistent extents, a table of the wrong bank
+    d = _desc(1, F32, 8, 2, [4096])
+    taps = (ctypes.c_double * 8)(*host_taps("db4")[0])
+    tab = _bwt.BwtTables(0, 2, 2)
+    null_details = (ctypes.c_void_p * 1)(None)
+    assert lib.mifwt_bwt_fwd(ctypes.byref(d), None, None, null_details, taps, taps, ctypes.byref(tab), None) == BADARG
+    bad = _desc(1, F32, 8, 2, [4096], coef=[2051])
+    assert lib.mifwt_bwt_fwd(ctypes.byref(bad), None, None, null_details, taps, taps, ctypes.byref(tab), None) == BADARG
+    assert lib.mifwt_bwt_inv(ctypes.byref(bad), None, null_details, None, taps, taps, ctypes.byref(tab), None) == BADARG
+    strides = (ctypes.c_int64 * 3)(4096, 1, 1)
+    assert lib.mifwt_bwt_axis_fwd(F32, 8, 0, 2, 4096, 1, None, strides, None, strides, None, strides, taps, taps, ctypes.byref(tab), None) == BADARG
+    assert OK == 0
+
+
+def test_bank_and_virtual_sample_rules():
+    taps = host_taps("bior2.2")
+    a, s = _bwt.bank(taps, "qr", "analysis"), _bwt.bank(taps, "gramschmidt", "synthesis")
+    assert a is _bwt.bank(taps, "gramschmidt", "analysis") and a is not s
+    assert a.f_lo == tuple(taps[0]) and s.f_lo == tuple(taps[2])[::-1] and (a.n_top, a.n_bot) == (1, 1)
+    assert not np.array_equal(a._host_tab, s._host_tab)  # biorthogonal: S != A^T, an adjoint must not borrow the other tables
+    o = host_taps("db3")
+    assert np.array_equal(_bwt.bank(o, "qr", "analysis")._host_tab, _bwt.bank(o, "qr", "synthesis")._host_tab)
+    n = 9
+    x = np.arange(n)
+    for mode, want in (("zero", None), ("constant", 8), ("reflect", 7), ("periodic", 0), ("symmetric", 8)):
+        src = _bwt.virtual_source(n, _engine.MODE_IDS[mode])
+        assert (None if src < 0 else x[src]) == want
+        pt = {"zero": "constant", "constant": "replicate", "reflect": "reflect", "periodic": "circular"}.get(mode)
+        if pt is not None:
+            ref = torch.nn.functional.pad(torch.arange(n, dtype=torch.float64).reshape(1, 1, n), (0, 1), mode=pt)[0, 0, -1]
+            assert float(ref) == (0.0 if src < 0 else float(x[src]))
+    assert _bwt.is_short([12], 8) and not _bwt.is_short([13], 8) and not _bwt.is_short([14], 8) and _bwt.is_short([64, 11], 8)
