@@ -9,6 +9,11 @@ stride-2 ``conv_transpose{1,2,3}d`` with the reconstruction filters, the crops a
 separable transforms = one 1-D level per axis (src/ptwt/separable_conv_transform.py).  Gradients w.r.t. the data and all four filters
 come from ``torch.autograd``, to any order.
 
+The stationary transform (``swt`` / ``iswt``, src/ptwt/stationary_transform.py:95-107, :142-156) is restated the same way: per level
+the circular extension by ``D (L/2 - 1)`` and ``D (L/2)`` samples (swapped for synthesis), the stride-1 correlation with dilation
+``D = 2^level`` and, for synthesis, the mean of the pair — written as index gathers of the closed form those ops amount to (any
+number of wraps around the row).
+
 A wavelet argument is either a name (taps from the committed pywt banks, float64 tensors) or a 4-tuple
 ``(dec_lo, dec_hi, rec_lo, rec_hi)`` of 1-D tensors, taken as they are (flips are ``torch.flip``, outer products ``torch.einsum``).
 3-D levels of more than :data:`DENSE_3D_MAX_TAPS` taps run as one 1-D level per axis (the same operator; a dense L^3 kernel is slow
@@ -238,3 +243,67 @@ def fswaverec2(coeffs, wavelet, *, axes=None) -> torch.Tensor:
 
 def fswaverec3(coeffs, wavelet, *, axes=None) -> torch.Tensor:
     return _fswaverec(coeffs, wavelet, 3, axes)
+
+
+# ---- stationary transform (src/ptwt/stationary_transform.py) ------------------------------------------------------------------------------
+def _circular_taps(x: torch.Tensor, flen: int, first: int, dilation: int) -> torch.Tensor:
+    """[B, N] -> [B, L, N]: plane m holds ``x[(n + first - D m) mod N]``, the sample tap m meets at output n once the row is extended
+    circularly and correlated with dilation D (the modulo takes any number of wraps)."""
+    n = x.shape[-1]
+    idx = (torch.arange(n).unsqueeze(0) + first - dilation * torch.arange(flen).unsqueeze(1)) % n
+    return x.index_select(1, idx.reshape(-1)).reshape(x.shape[0], flen, n)
+
+
+def _weighted(h: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """sum_m h[m] w[:, m, :] as a product and ``torch.sum`` (whose backward w.r.t. h is again a ``torch.sum``: pairwise summation, so a
+    float32 run of this module — the yardstick of the float32 gradient bounds on the GPU tier — does not add up a row sequentially)."""
+    return (h.to(w.dtype).reshape(1, -1, 1) * w).sum(1)
+
+
+def swt_level(x: torch.Tensor, dec_lo: torch.Tensor, dec_hi: torch.Tensor, dilation: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One analysis level of [B, N]: ``lo / hi[n] = sum_m h[m] x[(n + D (L/2 - m)) mod N]`` (pad left D (L/2 - 1), right D (L/2),
+    conv1d with the flipped filters)."""
+    flen = dec_lo.shape[0]
+    w = _circular_taps(x, flen, dilation * (flen // 2), dilation)
+    return _weighted(dec_lo, w), _weighted(dec_hi, w)
+
+
+def iswt_level(a: torch.Tensor, d: torch.Tensor, rec_lo: torch.Tensor, rec_hi: torch.Tensor, dilation: int) -> torch.Tensor:
+    """One synthesis level: ``y[n] = 1/2 sum_j g_lo[j] a[(n + D (L/2 - 1 - j)) mod N] + g_hi[j] d[...]`` (pad left D (L/2), right
+    D (L/2 - 1), grouped conv_transpose1d cropped by the pads, mean of the pair)."""
+    flen = rec_lo.shape[0]
+    first = dilation * (flen // 2 - 1)
+    return (_weighted(rec_lo, _circular_taps(a, flen, first, dilation)) + _weighted(rec_hi, _circular_taps(d, flen, first, dilation))) / 2
+
+
+def _swt_max_level(n: int) -> int:
+    """How often the extent can be halved (pywt.swt_max_level)."""
+    level = 0
+    while n > 0 and n % 2 == 0:
+        n //= 2
+        level += 1
+    return level
+
+
+def swt(data: torch.Tensor, wavelet, level: Optional[int] = None, *, axis: Optional[int] = None) -> List[torch.Tensor]:
+    """``[cA_n, cD_n, ..., cD_1]``, every entry shaped like the input."""
+    bank = bank_of(wavelet)
+    cur, meta = _fold(data, axis, 1)
+    if level is None:
+        level = _swt_max_level(cur.shape[-1])
+    out = []
+    for lvl in range(level):
+        cur, hi = swt_level(cur, bank[0], bank[1], 2 ** lvl)
+        out.append(_unfold(hi, meta))
+    out.append(_unfold(cur, meta))
+    return out[::-1]
+
+
+def iswt(coeffs, wavelet, *, axis: Optional[int] = None) -> torch.Tensor:
+    bank = bank_of(wavelet)
+    coeffs = list(coeffs)
+    cur, meta = _fold(coeffs[0], axis, 1)
+    details = coeffs[1:]
+    for pos, det in enumerate(details):
+        cur = iswt_level(cur, _fold(det, axis, 1)[0], bank[2], bank[3], 2 ** (len(details) - pos - 1))
+    return _unfold(cur, meta)

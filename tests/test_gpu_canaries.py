@@ -239,6 +239,24 @@ def test_canaries_gradients_packets_swt(guarded):
     _run(guarded, "WaveletPacket2D", lambda t: torch.stack([ptwt_amd.WaveletPacket2D(t, "db2", mode="reflect", maxlevel=2)[k] for k in ("aa", "dd")]), [p])
     s = _x(3, 256)
     _run(guarded, "swt / iswt", lambda t: ptwt_amd.iswt(ptwt_amd.swt(t, "db3", level=3), "db3"), [s])
+    # stationary levels whose last lanes are ragged (the extent is no multiple of a lane's 4 / 2 samples): the scalar tail stores of the
+    # last row end where the guard bytes begin, and the high-pass plane of an odd extent starts off the vector store's alignment
+    def both(wavelet, level):
+        def fn(t):
+            c = ptwt_amd.swt(t, wavelet, level=level)
+            return torch.stack(c + [ptwt_amd.iswt(c, wavelet)])
+        return fn
+    _run(guarded, "swt / iswt 3 x 1001 f32", both("db3", 3), [_x(3, 1001)])
+    _run(guarded, "swt / iswt 2 x 259 f64", both("db4", 2), [_x(2, 259, dtype=torch.float64)])
+    with ptwt_amd.half_storage():
+        _run(guarded, "swt / iswt 3 x 1001 f16", both("db2", 3), [_x(3, 1001, dtype=torch.float16)])
+    _run(guarded, "swt / iswt 2 x 300, 34 taps", both("db17", 2), [_x(2, 300)])
+    sb = tuple(torch.tensor(t, dtype=torch.float32, device=dev(), requires_grad=True) for t in taps)
+    def learn_swt(t):
+        c = ptwt_amd.swt(t, sb, level=2)
+        y = ptwt_amd.iswt(c, sb)
+        return torch.cat([g.reshape(-1) for g in torch.autograd.grad(c + [y], [t, *sb], [torch.ones_like(o) for o in c + [y]])])
+    _run(guarded, "swt / iswt tap gradients 3 x 1001", learn_swt, [_x(3, 1001).requires_grad_(True)])
 
 
 def test_canaries_offsets_beyond_two_gib(guarded):

@@ -136,6 +136,37 @@ def test_host_layer_vs_reference_goldens(case, oracle_engine):
     assert G.relerr(rec.numpy(), want) < (1e-11 if case["dtype"] == "float64" else 2e-6)
 
 
+def test_swt_host_layer_vs_reference_goldens(oracle_engine):
+    """Host logic of ``swt`` / ``iswt`` (fold / unfold of ``axis``, 1-D inputs, level count, dilation order, container order, the
+    autograd Functions' wiring) on the numpy level stand-ins, against every case of ptwt_ref_swt.npz: coefficients, reconstruction and
+    both data gradients at the bounds tests/test_gpu_swt.py uses on the GPU."""
+    z, idx = G.load("ptwt_ref_swt.npz")
+    assert len(idx) == 28
+
+    def weight(t, i):
+        return torch.cos(0.37 * torch.arange(t.numel(), dtype=torch.float64) + i).reshape(t.shape)
+
+    for case in idx:
+        k = case["key"]
+        x = torch.from_numpy(z[k + "_x"]).requires_grad_(True)
+        c = ptwt_amd.swt(x, case["wavelet"], case["level"], **case["kw"])
+        assert isinstance(c, list) and len(c) == case["ncoef"]
+        for i, t in enumerate(c):
+            want = z["%s_c%d" % (k, i)]
+            assert tuple(t.shape) == want.shape and t.dtype == torch.float64
+            assert G.relerr(t.detach().numpy(), want) < 1e-12, (case, i)
+        (gx,) = torch.autograd.grad(sum((weight(t, i) * t).sum() for i, t in enumerate(c)), x)
+        assert G.relerr(gx.numpy(), z[k + "_gx"]) < 1e-11, (case, "swt backward")
+        leaves = [t.detach().clone().requires_grad_(True) for t in c]
+        y = ptwt_amd.iswt(leaves, case["wavelet"], **case["kw"])
+        assert G.relerr(y.detach().numpy(), z[k + "_rec"]) < 1e-12, (case, "iswt")
+        for i, g in enumerate(torch.autograd.grad((weight(y, 7) * y).sum(), leaves)):
+            assert G.relerr(g.numpy(), z["%s_gc%d" % (k, i)]) < 1e-11, (case, "iswt backward", i)
+        with torch.no_grad():  # (the graph-free route calls the level binding directly)
+            for t, u in zip(ptwt_amd.swt(x, case["wavelet"], case["level"], **case["kw"]), c):
+                assert torch.equal(t, u.detach())
+
+
 def test_error_behaviour(oracle_engine):
     """Error types pinned by the reference (reference tests/test_convolution_fwt.py:347-402,
     tests/test_convolution_fwt_3.py:167-178)."""

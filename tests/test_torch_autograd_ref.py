@@ -3,7 +3,9 @@ tests/test_gpu_learnable_lengths.py.  Before it may judge anything it is pinned 
 produced — the values of tests/golden/ptwt_ref.npz, the data gradients of ptwt_ref_grads.npz, the tap gradients of
 ptwt_ref_tapgrads.npz and the second-order tap derivatives of ptwt_ref_tapgrads2.npz (level transforms only; fp64 1e-12 norm-wise, the
 second order 1e-11) — and against the independent numpy oracle (oracle/fwt_oracle.py) at long and odd filter lengths, with random
-four-filter banks, in all five modes."""
+four-filter banks, in all five modes.  Its stationary transform (``swt`` / ``iswt``) is pinned against every case of
+ptwt_ref_swt.npz and the swt cases of both tap-gradient goldens, and the numpy level stand-ins of tests/_oracle_engine.py
+(``swt_level_fwd`` / ``swt_level_inv``: the float64 oracle of single level calls in tests/test_gpu_swt_kernels.py) against it."""
 import numpy as np
 import pytest
 import torch
@@ -87,8 +89,8 @@ def test_data_gradients_vs_reference_goldens():
 
 def test_tap_gradients_vs_reference_goldens():
     z, idx = G.load("ptwt_ref_tapgrads.npz")
-    cases = [c for c in idx if not c["fn"].startswith(("swt", "packet"))]
-    assert len(cases) == 38
+    cases = [c for c in idx if not c["fn"].startswith("packet")]
+    assert len(cases) == 41 and sum(c["fn"] == "swt" for c in cases) == 3
     for case in cases:
         k, kw = case["key"], _kw(case)
         x = torch.from_numpy(z[k + "_x"])
@@ -105,8 +107,8 @@ def test_tap_gradients_vs_reference_goldens():
 
 def test_second_order_tap_derivatives_vs_reference_goldens():
     z, idx = G.load("ptwt_ref_tapgrads2.npz")
-    cases = [c for c in idx if not c["fn"].startswith(("swt", "packet"))]
-    assert cases
+    cases = [c for c in idx if not c["fn"].startswith("packet")]
+    assert cases and sum(c["fn"] == "swt" for c in cases) == 3
     for case in cases:
         k, kw = case["key"], _kw(case)
         x = torch.from_numpy(z[k + "_x"]).requires_grad_(True)
@@ -128,6 +130,29 @@ def test_second_order_tap_derivatives_vs_reference_goldens():
             assert G.relerr(got.numpy(), z["%s_s_dc%d" % (k, i)]) < 1e-11, (case, "s_dc", i)
         assert G.relerr(d2[-2].numpy(), z[k + "_s_dlo"]) < 1e-11, (case, "s_dlo")
         assert G.relerr(d2[-1].numpy(), z[k + "_s_dhi"]) < 1e-11, (case, "s_dhi")
+
+
+def test_swt_vs_reference_goldens():
+    """Every case of ptwt_ref_swt.npz (incl. axis=1, the 1-D input, windows that wrap more than once, 22 - 102 taps): coefficients,
+    reconstruction and both data gradients, at the bounds of tests/test_gpu_swt.py."""
+    z, idx = G.load("ptwt_ref_swt.npz")
+    assert len(idx) == 28 and any(c["kw"] for c in idx) and any(len(c["shape"]) == 1 for c in idx)
+    for case in idx:
+        k = case["key"]
+        x = torch.from_numpy(z[k + "_x"]).requires_grad_(True)
+        c = R.swt(x, case["wavelet"], case["level"], **case["kw"])
+        assert len(c) == case["ncoef"]
+        for i, t in enumerate(c):
+            want = z["%s_c%d" % (k, i)]
+            assert tuple(t.shape) == want.shape and t.dtype == torch.float64
+            assert G.relerr(t.detach().numpy(), want) < 1e-12, (case, i)
+        (gx,) = torch.autograd.grad(sum((weight(t, i) * t).sum() for i, t in enumerate(c)), x)
+        assert G.relerr(gx.numpy(), z[k + "_gx"]) < 1e-11, (case, "swt backward")
+        leaves = [t.detach().clone().requires_grad_(True) for t in c]
+        y = R.iswt(leaves, case["wavelet"], **case["kw"])
+        assert G.relerr(y.detach().numpy(), z[k + "_rec"]) < 1e-12, (case, "iswt")
+        for i, g in enumerate(torch.autograd.grad((weight(y, 7) * y).sum(), leaves)):
+            assert G.relerr(g.numpy(), z["%s_gc%d" % (k, i)]) < 1e-11, (case, "iswt backward", i)
 
 
 def random_bank(flen, seed):
@@ -194,3 +219,27 @@ def test_3d_per_axis_form_equals_dense_form(flen):
             R.DENSE_3D_MAX_TAPS = saved
     for a, b in zip(*outs):
         assert G.relerr(a.detach().numpy(), b.detach().numpy()) < 1e-12
+
+
+# (N, L, D): odd extents, rows shorter than one tap step, D L > 2 N (windows that wrap several times), D L/2 a multiple of N
+STANDIN_CELLS = [(1, 4, 2), (3, 8, 1), (5, 2, 3), (24, 16, 4), (37, 6, 2), (41, 22, 8), (257, 10, 64), (48, 12, 8), (1001, 34, 3)]
+
+
+@pytest.mark.parametrize("n,flen,dilation", STANDIN_CELLS)
+@pytest.mark.parametrize("scale", [1.0, 0.5, float(np.pi / 7)])
+def test_numpy_level_stand_ins_vs_reference(n, flen, dilation, scale):
+    """``swt_level_fwd`` / ``swt_level_inv`` (tests/_oracle_engine.py) against one level of the reference with four independent random
+    filters: what makes them a legitimate float64 oracle for single level calls on the GPU tier (any dilation, any scale)."""
+    from tests import _oracle_engine as oe
+
+    bank = random_bank(flen, 3 * n + flen)
+    tb = [torch.from_numpy(f) for f in bank]
+    g = torch.Generator().manual_seed(n + dilation)
+    x, a, d = (torch.randn(3, n, generator=g, dtype=torch.float64) for _ in range(3))
+    lo, hi = R.swt_level(x, tb[0], tb[1], dilation)
+    got = oe.swt_level_fwd(x, list(bank[0]), list(bank[1]), dilation, scale)
+    assert got.dtype == torch.float64 and got.shape == (3, 2, n)
+    assert G.relerr(got[:, 0].numpy(), scale * lo.numpy()) < 1e-13 and G.relerr(got[:, 1].numpy(), scale * hi.numpy()) < 1e-13
+    y = R.iswt_level(a, d, tb[2], tb[3], dilation)  # (the reference's level carries the mean of the pair: scale 1/2)
+    got = oe.swt_level_inv(a, d, list(bank[2]), list(bank[3]), dilation, scale)
+    assert got.shape == (3, n) and G.relerr(got.numpy(), 2 * scale * y.numpy()) < 1e-13
