@@ -22,7 +22,7 @@ import torch
 from . import _boundary, _engine
 
 KID_FWD, KID_INV, KID_AXIS_FWD, KID_AXIS_INV = 26, 27, 28, 29
-_ZERO = _engine.MODE_IDS["zero"]
+_ZERO, _REFLECT = _engine.MODE_IDS["zero"], _engine.MODE_IDS["reflect"]
 
 
 class BwtTables(ctypes.Structure):
@@ -157,6 +157,9 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
     sig = [int(n) for n in x.shape[1:]]
     coef = [(n + 1) // 2 for n in sig]
     L = bk.filt_len
+    if mode_id == _REFLECT and 1 in sig:
+        # (an odd extent of one sample has nothing to reflect: torch's reflection padding, which the reference uses, refuses it too)
+        raise ValueError("odd_coeff_padding_mode='reflect' needs at least two samples along every transformed axis")
     if is_short(sig, L):
         return _rows_dense(x, bk, mode_id)
     x = _unit_last(x)

@@ -1,5 +1,7 @@
 """Host-side tests of the boundary-wavelet transforms (no GPU): the boundary tables against the reference's matrices
-(tests/golden/ptwt_ref_boundary.npz, group "blocks"), the public interface and its errors, and the host half of the C ABI."""
+(tests/golden/ptwt_ref_boundary.npz, group "blocks"), the public interface and its errors, the host half of the C ABI, and the
+float64 level operators as a reference chain (tests/_boundary_ref.py) against the reference's classes at mid sizes
+(tests/golden/ptwt_ref_boundary_mid.npz)."""
 import ctypes
 import inspect
 import io
@@ -258,3 +260,112 @@ def test_bank_and_virtual_sample_rules():
             ref = torch.nn.functional.pad(torch.arange(n, dtype=torch.float64).reshape(1, 1, n), (0, 1), mode=pt)[0, 0, -1]
             assert float(ref) == (0.0 if src < 0 else float(x[src]))
     assert _bwt.is_short([12], 8) and not _bwt.is_short([13], 8) and not _bwt.is_short([14], 8) and _bwt.is_short([64, 11], 8)
+
+
+# ---- the float64 operators as the reference of the GPU kernel tests: pinned to the reference library at L = 10 .. 18 and mid sizes --------
+MID = "ptwt_ref_boundary_mid.npz"
+MID_WAVELETS = ("db5", "db6", "db7", "db9", "sym7", "coif3", "bior4.4")
+
+
+def test_tables_match_the_reference_blocks_at_the_lengths_the_first_fixture_misses():
+    """L = 10, 12, 14 and 18 (db5, db6, db7 / sym7, db9 / coif3) and the biorthogonal bior4.4, gramschmidt: exact in sign, 1e-12 on
+    entries."""
+    z, idx = G.load(MID)
+    blocks = [c for c in idx if c["group"] == "blocks"]
+    assert tuple(c["wavelet"] for c in blocks) == MID_WAVELETS and {c["filt_len"] for c in blocks} == {10, 12, 14, 18}
+    for case in blocks:
+        taps = host_taps(case["wavelet"])
+        assert len(taps[0]) == case["filt_len"]
+        nt, nb = _boundary.boundary_rows(case["filt_len"])
+        for which in ("analysis", "synthesis"):
+            got = _boundary.boundary_blocks(taps, "gramschmidt", which)
+            for band in ("lo", "hi"):
+                for end, rows in (("top", nt), ("bot", nb)):
+                    want = z["%s_%s_%s_%s" % (case["key"], which, band, end)]
+                    mine = got["%s_%s" % (band, end)]
+                    assert mine.shape == want.shape == (rows, case["filt_len"] - 1)
+                    assert np.abs(mine - want).max(initial=0.0) < 1e-12, (case, which, band, end)
+
+
+def _flat_golden(z, case, stem):
+    return [torch.from_numpy(z["%s_%s%d" % (case["key"], stem, i)]) for i in range(case["ncoef"])]
+
+
+def test_level_operators_reproduce_the_reference_at_mid_sizes():
+    """``level_coo`` / ``level_matrix`` applied in float64 on the CPU (tests/_boundary_ref.py: sparse for rows, dense for planes, the
+    virtual sample of an odd extent by mode) against the reference's classes at 2110 and 4101 samples and planes of 70 x 150 and
+    67 x 133, L = 8, 14 and 18, every non-zero ``odd_coeff_padding_mode``: coefficients and reconstruction to 1e-12 (a comparison with
+    the live reference at (2, 2110) and (1, 70, 150) showed 2e-14 at worst), the recorded gradients to 1e-11."""
+    from tests import _boundary_ref as BR
+
+    z, idx = G.load(MID)
+    cases = [c for c in idx if c["group"] == "gs"]
+    assert {(c["ndim"], c["filt_len"]) for c in cases} >= {(1, 8), (1, 14), (1, 18), (2, 8), (2, 18)}
+    assert {c["kw"].get("odd_coeff_padding_mode", "zero") for c in cases if c["padded"]} == set(BR.MODES)
+    assert {c["ndim"] for c in cases if c["grads"]} == {1, 2}
+    weight = lambda t, i: torch.cos(0.37 * torch.arange(t.numel(), dtype=torch.float64) + i).reshape(t.shape)  # noqa: E731
+    for case in cases:
+        taps = host_taps(case["wavelet"])
+        mode = case["kw"].get("odd_coeff_padding_mode", "zero")
+        x = torch.from_numpy(z[case["key"] + "_x"]).double().requires_grad_(True)
+        assert list(x.shape) == case["shape"]
+        c = BR.wavedec(x, taps, case["level"], mode)
+        want = _flat_golden(z, case, "c")
+        assert len(c) == len(want) == case["ncoef"]
+        for i, (a, b) in enumerate(zip(c, want)):
+            assert G.relerr(a.detach().numpy(), b.numpy()) < 1e-12, (case, "coefficient", i)
+        leaves = [t.clone().requires_grad_(True) for t in want]
+        y = BR.waverec(leaves, taps, case["ndim"])
+        assert G.relerr(y.detach().numpy(), z[case["key"] + "_rec"]) < 1e-12, (case, "reconstruction")
+        if case["grads"]:
+            (gx,) = torch.autograd.grad(sum((weight(t, i) * t).sum() for i, t in enumerate(c)), x)
+            assert G.relerr(gx.numpy(), z[case["key"] + "_gx"]) < 1e-11, (case, "analysis backward")
+            gl = torch.autograd.grad((weight(y, 7) * y).sum(), leaves)
+            for i, g in enumerate(gl):
+                assert G.relerr(g.numpy(), z["%s_gc%d" % (case["key"], i)]) < 1e-11, (case, "synthesis backward", i)
+
+
+@pytest.mark.parametrize("flen", list(range(2, 22, 2)) + [22, 34, 76, 128])
+def test_level_coo_and_level_matrix_agree_entry_for_entry(flen):
+    """One even length per L, four independent random filters (``_boundary`` accepts any taps), both directions: the sparse triplets
+    are the dense matrix, entry for entry and without duplicates."""
+    g = np.random.default_rng(flen)
+    taps = tuple(tuple(float(v) for v in g.standard_normal(flen) / np.sqrt(flen)) for _ in range(4))
+    n = 2 * (flen - 1) + 2 * (flen % 7) + 6
+    for which in ("analysis", "synthesis"):
+        dense = _boundary.level_matrix(taps, n, "qr", which)
+        r, c, v = _boundary.level_coo(taps, n, "qr", which)
+        assert len(set(zip(r.tolist(), c.tolist()))) == len(r)
+        sparse = np.zeros((n, n))
+        sparse[r, c] = v
+        assert np.array_equal(sparse, dense), (flen, which)
+        assert np.count_nonzero(dense) <= len(v)
+    # the rows of the synthesis bank are built from the reversed rec_* filters, not from the dec_* ones
+    assert not np.array_equal(_boundary.level_matrix(taps, n, "qr", "synthesis").T, _boundary.level_matrix(taps, n, "qr", "analysis"))
+
+
+def test_tile_table_of_the_gpu_kernel_tests_is_the_geometry_of_the_source():
+    """tests/test_gpu_boundary_kernels.py places its extents around the tile widths; the table it states is read against
+    ``FwdTile`` / ``InvTile`` of csrc/mifwt_bwt.hip here, so that a change of the geometry cannot leave the cells behind."""
+    import os
+    import re
+
+    from tests import test_gpu_boundary_kernels as K
+
+    with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_bwt.hip")) as f:
+        src = f.read()
+
+    def const(name):
+        (expr,) = re.findall(r"static constexpr int %s = ([^;]+);" % name, src)
+        return expr.strip()
+
+    assert re.search(r"struct BwtVec<float> \{\s*static constexpr int E = 4;", src) and re.search(r"struct BwtVec<double> \{\s*static constexpr int E = 2;", src)
+    assert K.E == {torch.float32: 4, torch.float64: 2}
+    assert (const("TC1"), const("TC"), const("TR")) == ("256 * E", "16 * E", "8")
+    assert (const("TQ1"), const("TQ"), const("TQC")) == ("128 * E", "16", "(L <= 12 ? 16 : 8) * E")
+    for dtype, e in K.E.items():
+        assert K.TILE1[("fwd", dtype)] == 256 * e and K.TILE1[("inv", dtype)] == 128 * e
+        for flen in K.FUSED:
+            assert K.tile2("fwd", dtype, flen) == (8, 16 * e) and K.tile2("inv", dtype, flen) == (16, (16 if flen <= 12 else 8) * e)
+    assert "g((unsigned)(blocks < 8192 ? blocks : 8192)), blk(256)" in src and K.GENERIC_GRID == 8192 * 256
+    assert K.FUSED == list(range(2, 21, 2)) and all("MIFWT_BWT_CASE(%d)" % flen in src for flen in K.FUSED)
