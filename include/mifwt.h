@@ -364,6 +364,26 @@ int mifwt_bwt_axis_inv(int dtype, int filt_len, int64_t outer, int64_t n, int64_
                        const void* hi_in, const int64_t* hi_strides, void* y, const int64_t* y_strides, const double* lo, const double* hi,
                        const mifwt_bwt_tables* tables, void* stream);
 
+/* THREE transformed axes (ptwt.MatrixWavedec3 / MatrixWaverec3, src/ptwt/matmul_transform_3.py: the level operator applied along width,
+ * height and depth): one fused launch per level (kernel ids 30 / 31, csrc/mifwt_bwt3.hip) that reads the volume once and writes the eight
+ * bands once.  ENVELOPE: f32 / f64, even L <= 8, unit innermost strides, every axis at least 2 (L-1) samples.
+ *   desc      ndim = 3; extents (depth, height, width) as for mifwt_bwt_fwd; `details` = 7 pointers that share detail_stride, detail
+ *             s-1 = band s with bit 2 of s = high-pass along depth, bit 1 along height, bit 0 along width (the order of mifwt_dwt_fwd)
+ * Tap order, table layout (the same struct, one table for all three axes) and the adjoint rules are those of mifwt_bwt_fwd / _inv.
+ * mifwt_bwt3_supported / mifwt_bwt3_kernel_id: 1 / 30 (direction 0) or 31 (direction 1) where the fused kernel serves the level;
+ * 0 / MIFWT_ERR_UNSUPPORTED where it does not (L above the envelope, f16, a non-unit innermost stride, an axis shorter than 2 (L-1),
+ * extents beyond the kernels' index range; mifwt_bwt3_fwd / _inv then launch nothing and return MIFWT_ERR_UNSUPPORTED: run the axis passes
+ * 28 / 29); MIFWT_ERR_BADARG for ndim != 3, an odd or too long L, coef_extent != ceil(sig_extent / 2), an axis shorter than L, an unknown
+ * dtype or mode, or null pointers.  mifwt_bwt_supported / mifwt_bwt_kernel_id keep declining ndim == 3. */
+#define MIFWT_KID_BWT3_FWD 30
+#define MIFWT_KID_BWT3_INV 31
+int mifwt_bwt3_supported(const mifwt_level_desc* desc, int direction);
+int mifwt_bwt3_kernel_id(const mifwt_level_desc* desc, int direction);
+int mifwt_bwt3_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* lo, const double* hi,
+                   const mifwt_bwt_tables* tables, void* stream);
+int mifwt_bwt3_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* lo, const double* hi,
+                   const mifwt_bwt_tables* tables, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -417,7 +437,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          mifwt_dwt2_inv_pyramid; likewise)
  *   22     up to three fused 2-D synthesis levels of a big plane per launch (mifwt_dwt2_inv_pyramid's second kernel; likewise)
  *   26 / 27  fused boundary-wavelet analysis / synthesis level, 1-D and 2-D (mifwt_bwt_fwd / mifwt_bwt_inv; answered by mifwt_bwt_kernel_id)
- *   28 / 29  one axis of a boundary-wavelet level through a run-time tap loop (mifwt_bwt_axis_fwd / mifwt_bwt_axis_inv) */
+ *   28 / 29  one axis of a boundary-wavelet level through a run-time tap loop (mifwt_bwt_axis_fwd / mifwt_bwt_axis_inv)
+ *   30 / 31  fused 3-D boundary-wavelet analysis / synthesis level, LDS bricks (mifwt_bwt3_fwd / mifwt_bwt3_inv; f32 / f64, even L <= 8;
+ *          answered by mifwt_bwt3_kernel_id) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

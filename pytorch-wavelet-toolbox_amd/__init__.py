@@ -27,6 +27,7 @@ from .packets import WaveletPacket, WaveletPacket2D
 from .stationary_transform import iswt, swt
 from .matmul_transform import MatrixWavedec, MatrixWaverec
 from .matmul_transform_2 import MatrixWavedec2, MatrixWaverec2
+from .matmul_transform_3 import MatrixWavedec3, MatrixWaverec3
 from .separable_conv_transform import fswavedec2, fswavedec3, fswaverec2, fswaverec3
 from .graphs import CapturedCall, capture
 from ._wavelets import set_device_taps
@@ -62,6 +63,8 @@ __all__ = [
     "MatrixWaverec",
     "MatrixWavedec2",
     "MatrixWaverec2",
+    "MatrixWavedec3",
+    "MatrixWaverec3",
     "capture",
     "CapturedCall",
 ]

@@ -8,13 +8,14 @@ built from them.  Two level maps exist,
 
 each one fused launch per level (kernel ids 26 / 27) for float32 / float64, even ``L <= 20`` and axes of at least ``2 (L-1)``
 samples; longer filters run one generic launch per axis (28 / 29); a level with an axis shorter than ``2 (L-1)`` — a few dozen
-samples — is a dense ``torch.matmul`` with the small level matrix.  The tables are cached per bank and uploaded once per device;
+samples — is a dense ``torch.matmul`` with the small level matrix.  Three transformed axes have kernels of their own (ids 30 / 31,
+csrc/mifwt_bwt3.hip: even ``L <= 8``); what they decline runs the axis passes width, height, depth — seven launches per level.  The tables are cached per bank and uploaded once per device;
 after that a call allocates its outputs and enqueues launches, nothing else: no host round trip, capturable.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 import torch
@@ -22,7 +23,21 @@ import torch
 from . import _boundary, _engine
 
 KID_FWD, KID_INV, KID_AXIS_FWD, KID_AXIS_INV = 26, 27, 28, 29
+KID_FWD3, KID_INV3 = 30, 31
+
 _ZERO, _REFLECT = _engine.MODE_IDS["zero"], _engine.MODE_IDS["reflect"]
+
+# Tests and tools/boundary_bench.py set this to run a 3-D level through the composed axis passes although the fused kernel would take it.
+FORCE_COMPOSED3 = False
+# (direction, dtype, L) cells of the fused 3-D envelope that go to the composed passes all the same (direction 0 analysis, 1 synthesis).
+# A cell belongs to the bricks only where `tools/boundary_bench.py --shape cells` has shown the fused median ahead of the composed one by
+# more than the spread of its windows (EXPERIMENTS.md part B).  The synthesis bricks for 6 and 8 taps hold a CU alone (100 - 150 KB of
+# LDS, csrc/mifwt_bwt3.hip) and have no such measurement: they are routed to the axis passes.
+COMPOSED3_CELLS: Set[Tuple[int, torch.dtype, int]] = {(1, dt, flen) for dt in (torch.float32, torch.float64) for flen in (6, 8)}
+
+
+def _composed3(direction: int, dtype: torch.dtype, flen: int) -> bool:
+    return FORCE_COMPOSED3 or (direction, dtype, flen) in COMPOSED3_CELLS
 
 
 class BwtTables(ctypes.Structure):
@@ -41,13 +56,17 @@ def _lib():
         vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
         dbl_p, desc_p, tab_p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_engine.LevelDesc), ctypes.POINTER(BwtTables)
         i64_p, vpp = ctypes.POINTER(i64), ctypes.POINTER(vp)
-        for name in ("mifwt_bwt_supported", "mifwt_bwt_kernel_id"):
+        for name in ("mifwt_bwt_supported", "mifwt_bwt_kernel_id", "mifwt_bwt3_supported", "mifwt_bwt3_kernel_id"):
             getattr(lib, name).restype = ci
             getattr(lib, name).argtypes = [desc_p, ci]
         lib.mifwt_bwt_fwd.restype = ci
         lib.mifwt_bwt_fwd.argtypes = [desc_p, vp, vp, vpp, dbl_p, dbl_p, tab_p, vp]
         lib.mifwt_bwt_inv.restype = ci
         lib.mifwt_bwt_inv.argtypes = [desc_p, vp, vpp, vp, dbl_p, dbl_p, tab_p, vp]
+        for name in ("mifwt_bwt3_fwd", "mifwt_bwt3_inv"):
+            getattr(lib, name).restype = ci
+        lib.mifwt_bwt3_fwd.argtypes = lib.mifwt_bwt_fwd.argtypes
+        lib.mifwt_bwt3_inv.argtypes = lib.mifwt_bwt_inv.argtypes
         lib.mifwt_bwt_axis_fwd.restype = ci
         lib.mifwt_bwt_axis_fwd.argtypes = [ci, ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
         lib.mifwt_bwt_axis_inv.restype = ci
@@ -145,13 +164,19 @@ def _unit_last(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 or t.shape[-1] == 1 and t.is_contiguous() else t.contiguous()
 
 
-def _strides3(t: torch.Tensor):
+def _axis_strides(t: torch.Tensor):
+    """(outer, axis, inner) strides of an [outer, n, inner] view, as the axis passes 28 / 29 take them."""
     return _engine._arr(ctypes.c_int64, 3)(*t.stride())
+
+
+def _outer_axis_inner(t: torch.Tensor, axis: int) -> torch.Tensor:
+    """A dense [B, d0, d1, d2] tensor as the [outer, n, inner] view whose middle axis is ``axis`` (1 .. 3)."""
+    return t.reshape(int(np.prod(t.shape[:axis])), t.shape[axis], int(np.prod(t.shape[axis + 1:])))
 
 
 # ---- the two level maps (no autograd) ---------------------------------------------------------------------------------------------
 def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
-    """x [B, n0(, n1)] -> buffer [B, 2^d, M0(, M1)], plane s = band s (bit (d-1-a) of s set <=> high-pass along axis a)."""
+    """x [B, n0(, n1(, n2))] -> buffer [B, 2^d, M0(, M1(, M2))], plane s = band s (bit (d-1-a) of s set <=> high-pass along axis a)."""
     _engine._require_gpu(x)
     ndim = x.dim() - 1
     sig = [int(n) for n in x.shape[1:]]
@@ -173,17 +198,20 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
         bs = list(buf.stride())
         st = [bs[0]] + bs[2:]
         d = _desc(ndim, x.dtype, mode_id, L, x.shape[0], sig, x.stride(), coef, st, st)
-        kid = lib.mifwt_bwt_kernel_id(ctypes.byref(d), 0)
+        kid = (lib.mifwt_bwt3_kernel_id if ndim == 3 else lib.mifwt_bwt_kernel_id)(ctypes.byref(d), 0)
         if kid < 0 and kid != -2:
             _engine._check(kid)
         p = _plans[key] = (d, ctypes.byref(d), kid, bs[1] * x.element_size())
     d, ref, kid, plane = p
+    if kid == KID_FWD3 and _composed3(0, x.dtype, L):
+        kid = -2
     tab = bk.tables(x.device)
     lo, hi = _engine._taps_array(bk.f_lo), _engine._taps_array(bk.f_hi)
-    if kid == KID_FWD:
+    if kid in (KID_FWD, KID_FWD3):
         base, xp = buf.data_ptr(), x.data_ptr()
         ptrs = _engine._band_ptrs(base, plane, (1 << ndim) - 1)
-        _launch(0, kid, sig, x, lambda stream: lib.mifwt_bwt_fwd(ref, xp, base, ptrs, lo, hi, ctypes.byref(tab), stream))
+        entry = lib.mifwt_bwt3_fwd if kid == KID_FWD3 else lib.mifwt_bwt_fwd
+        _launch(0, kid, sig, x, lambda stream: entry(ref, xp, base, ptrs, lo, hi, ctypes.byref(tab), stream))
         return buf
     if x.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"Input dtype {x.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
@@ -191,8 +219,8 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
 
     def axis_fwd(src, n, outer, inner, out_lo, out_hi, mode):
         _launch(0, KID_AXIS_FWD, (n,), src, lambda stream: lib.mifwt_bwt_axis_fwd(
-            dt, L, mode, outer, n, inner, src.data_ptr(), _strides3(src), out_lo.data_ptr(), _strides3(out_lo), out_hi.data_ptr(),
-            _strides3(out_hi), lo, hi, ctypes.byref(tab), stream))
+            dt, L, mode, outer, n, inner, src.data_ptr(), _axis_strides(src), out_lo.data_ptr(), _axis_strides(out_lo), out_hi.data_ptr(),
+            _axis_strides(out_hi), lo, hi, ctypes.byref(tab), stream))
 
     if ndim == 1:
         axis_fwd(x.unsqueeze(-1), sig[0], x.shape[0], 1, buf[:, 0].unsqueeze(-1), buf[:, 1].unsqueeze(-1), mode_id)
@@ -203,13 +231,26 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
         axis_fwd(x.reshape(b * n0, n1, 1), n1, b * n0, 1, tmp[0].reshape(b * n0, coef[1], 1), tmp[1].reshape(b * n0, coef[1], 1), mode_id)
         axis_fwd(tmp[0], n0, b, coef[1], buf[:, 0], buf[:, 2], mode_id)
         axis_fwd(tmp[1], n0, b, coef[1], buf[:, 1], buf[:, 3], mode_id)
+    elif ndim == 3:
+        # width, height, depth: 1 + 2 + 4 launches
+        x = x.contiguous()
+        b, n0, n1, n2 = x.shape
+        t_w = torch.empty((2, b, n0, n1, coef[2]), dtype=x.dtype, device=x.device)
+        axis_fwd(_outer_axis_inner(x, 3), n2, b * n0 * n1, 1, _outer_axis_inner(t_w[0], 3), _outer_axis_inner(t_w[1], 3), mode_id)
+        t_h = torch.empty((4, b, n0, coef[1], coef[2]), dtype=x.dtype, device=x.device)
+        for wb in range(2):
+            axis_fwd(_outer_axis_inner(t_w[wb], 2), n1, b * n0, coef[2], _outer_axis_inner(t_h[wb], 2), _outer_axis_inner(t_h[2 + wb], 2),
+                     mode_id)
+        for pl in range(4):
+            axis_fwd(_outer_axis_inner(t_h[pl], 1), n0, b, coef[1] * coef[2], buf[:, pl].reshape(b, coef[0], -1),
+                     buf[:, 4 + pl].reshape(b, coef[0], -1), mode_id)
     else:
-        raise NotImplementedError("boundary-wavelet levels exist for one and two transformed axes")
+        raise NotImplementedError("boundary-wavelet levels exist for one, two and three transformed axes")
     return buf
 
 
 def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequence[int]) -> torch.Tensor:
-    """bands (2^d tensors [B, M0(, M1)], band order as above) -> y [B, n0(, n1)], n in {2 M, 2 M - 1} per axis."""
+    """bands (2^d tensors [B, M0(, M1(, M2))], band order as above) -> y [B, n0(, n1(, n2))], n in {2 M, 2 M - 1} per axis."""
     a0 = bands[0]
     _engine._require_gpu(a0)
     ndim = a0.dim() - 1
@@ -229,18 +270,21 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
     p = _plans.get(key)
     if p is None:
         d = _desc(ndim, a0.dtype, _ZERO, L, a0.shape[0], sig, y.stride(), coef, bands[0].stride(), bands[1].stride())
-        kid = lib.mifwt_bwt_kernel_id(ctypes.byref(d), 1)
+        kid = (lib.mifwt_bwt3_kernel_id if ndim == 3 else lib.mifwt_bwt_kernel_id)(ctypes.byref(d), 1)
         if kid < 0 and kid != -2:
             _engine._check(kid)
         p = _plans[key] = (d, ctypes.byref(d), kid, 0)
     d, ref, kid, _ = p
+    if kid == KID_INV3 and _composed3(1, a0.dtype, L):
+        kid = -2
     tab = bk.tables(a0.device)
-    if kid == KID_INV:
+    if kid in (KID_INV, KID_INV3):
         # (the C entry takes the filters in rec order and reverses them into row filters)
         lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
         ptrs = _engine._arr(ctypes.c_void_p, len(bands) - 1)(*[t.data_ptr() for t in bands[1:]])
         ap, yp = bands[0].data_ptr(), y.data_ptr()
-        _launch(1, kid, sig, a0, lambda stream: lib.mifwt_bwt_inv(ref, ap, ptrs, yp, lo, hi, ctypes.byref(tab), stream))
+        entry = lib.mifwt_bwt3_inv if kid == KID_INV3 else lib.mifwt_bwt_inv
+        _launch(1, kid, sig, a0, lambda stream: entry(ref, ap, ptrs, yp, lo, hi, ctypes.byref(tab), stream))
         return y
     if a0.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"Input dtype {a0.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
@@ -249,7 +293,7 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
 
     def axis_inv(c_lo, c_hi, n, outer, inner, out):
         _launch(1, KID_AXIS_INV, (n,), c_lo, lambda stream: lib.mifwt_bwt_axis_inv(
-            dt, L, outer, n, inner, c_lo.data_ptr(), _strides3(c_lo), c_hi.data_ptr(), _strides3(c_hi), out.data_ptr(), _strides3(out),
+            dt, L, outer, n, inner, c_lo.data_ptr(), _axis_strides(c_lo), c_hi.data_ptr(), _axis_strides(c_hi), out.data_ptr(), _axis_strides(out),
             lo, hi, ctypes.byref(tab), stream))
 
     if ndim == 1:
@@ -261,8 +305,21 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
         axis_inv(bands[1], bands[3], sig[0], b, coef[1], tmp[1])
         axis_inv(tmp[0].reshape(b * sig[0], coef[1], 1), tmp[1].reshape(b * sig[0], coef[1], 1), sig[1], b * sig[0], 1,
                  y.reshape(b * sig[0], sig[1], 1))
+    elif ndim == 3:
+        # depth, height, width: 4 + 2 + 1 launches
+        b = a0.shape[0]
+        bands = [t.contiguous() for t in bands]
+        t_d = torch.empty((4, b, sig[0], coef[1], coef[2]), dtype=a0.dtype, device=a0.device)
+        for pl in range(4):
+            axis_inv(_outer_axis_inner(bands[pl], 1), _outer_axis_inner(bands[4 + pl], 1), sig[0], b, coef[1] * coef[2],
+                     _outer_axis_inner(t_d[pl], 1))
+        t_h = torch.empty((2, b, sig[0], sig[1], coef[2]), dtype=a0.dtype, device=a0.device)
+        for wb in range(2):
+            axis_inv(_outer_axis_inner(t_d[wb], 2), _outer_axis_inner(t_d[2 + wb], 2), sig[1], b * sig[0], coef[2],
+                     _outer_axis_inner(t_h[wb], 2))
+        axis_inv(_outer_axis_inner(t_h[0], 3), _outer_axis_inner(t_h[1], 3), sig[2], b * sig[0] * sig[1], 1, _outer_axis_inner(y, 3))
     else:
-        raise NotImplementedError("boundary-wavelet levels exist for one and two transformed axes")
+        raise NotImplementedError("boundary-wavelet levels exist for one, two and three transformed axes")
     return y
 
 
@@ -283,6 +340,12 @@ def _rows_dense(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
     if ndim == 1:
         c = x @ bk.dense(x.shape[1], x.device, x.dtype).T
         return c.reshape(x.shape[0], 2, -1)
+    if ndim == 3:
+        m_d, m_r, m_c = (bk.dense(x.shape[1 + a], x.device, x.dtype) for a in range(3))
+        c = m_r @ x @ m_c.T
+        c = (m_d @ c.transpose(1, 2)).transpose(1, 2)
+        d, h, w = (n // 2 for n in c.shape[1:])
+        return c.reshape(x.shape[0], 2, d, 2, h, 2, w).permute(0, 1, 3, 5, 2, 4, 6).reshape(x.shape[0], 8, d, h, w)
     m_r = bk.dense(x.shape[1], x.device, x.dtype)
     m_c = bk.dense(x.shape[2], x.device, x.dtype)
     c = m_r @ x @ m_c.T
@@ -297,6 +360,13 @@ def _transposed_dense(bands: Sequence[torch.Tensor], bk: Bank, sig: Sequence[int
         c = torch.cat([bands[0], bands[1]], -1)
         y = c @ bk.dense(c.shape[-1], a0.device, a0.dtype)
         return y[:, : sig[0]]
+    if ndim == 3:
+        halves = [torch.cat([torch.cat([bands[q], bands[q + 1]], -1), torch.cat([bands[q + 2], bands[q + 3]], -1)], -2) for q in (0, 4)]
+        c = torch.cat(halves, -3)
+        m_d, m_r, m_c = (bk.dense(c.shape[1 + a], a0.device, a0.dtype) for a in range(3))
+        y = m_r.T @ c @ m_c
+        y = (m_d.T @ y.transpose(1, 2)).transpose(1, 2)
+        return y[:, : sig[0], : sig[1], : sig[2]]
     c = torch.cat([torch.cat([bands[0], bands[1]], -1), torch.cat([bands[2], bands[3]], -1)], -2)
     y = bk.dense(c.shape[1], a0.device, a0.dtype).T @ c @ bk.dense(c.shape[2], a0.device, a0.dtype)
     return y[:, : sig[0], : sig[1]]

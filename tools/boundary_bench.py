@@ -9,7 +9,14 @@ Device events; every leg warmed; a timed window of at least 0.2 s per leg; the l
 max over the repeats.  One JSON line per shape: microseconds per call, the two ratios, and the share of the 8 TB/s HBM peak on the
 compulsory bytes (input + coefficients, from the shapes).
 
-    python tools/boundary_bench.py [--repeats 5] [--shape 2d|1d]
+The 3-D section (MatrixWavedec3 / MatrixWaverec3, --shape 3d) has the same protocol and four legs per direction: the fused route
+(kernel ids 30 / 31), the composed route of the same library (the axis passes 28 / 29, forced by ``_bwt.FORCE_COMPOSED3``, alternating
+with the fused leg in the same process), wavedec3 / waverec3 with mode="zero", and the level operators through torch.sparse.mm.
+--shape cells times ONE level per (direction, dtype, L) cell of the fused envelope, fused against composed: the routing table
+``_bwt.COMPOSED3_CELLS`` is filled from its verdicts (fused only where its median beats the composed median by more than the spread of
+the windows).
+
+    python tools/boundary_bench.py [--repeats 5] [--shape 2d|1d|3d|cells]
 """
 import argparse
 import json
@@ -118,10 +125,150 @@ def bench(shape, wavelet, level, repeats):
     print(json.dumps(res), flush=True)
 
 
+def sparse_legs3(x, wavelet, level):
+    """MatrixWavedec3 / MatrixWaverec3 as the reference runs them: one torch.sparse.mm per axis and level."""
+    taps = host_taps(wavelet)
+    banks = {"analysis": _bwt.bank(taps, "qr", "analysis"), "synthesis": _bwt.bank(taps, "qr", "synthesis")}
+    ops = {}
+
+    def op(which, n):
+        if (which, n) not in ops:
+            ops[which, n] = _bwt.sparse_level(banks[which], n, x.device, x.dtype)
+        return ops[which, n]
+
+    def along(which, t, dim):
+        t = t.transpose(dim, -1)
+        shape = t.shape
+        out = torch.sparse.mm(op(which, shape[-1]), t.reshape(-1, shape[-1]).T).T
+        return out.reshape(shape).transpose(dim, -1)
+
+    def dec():
+        lll, out = x, []
+        for _ in range(level):
+            pad = [v for n in reversed(lll.shape[1:]) for v in (0, n % 2)]
+            lll = torch.nn.functional.pad(lll, pad) if any(pad) else lll
+            for dim in (3, 2, 1):
+                lll = along("analysis", lll, dim)
+            b, d, h, w = lll.shape
+            planes = lll.reshape(b, 2, d // 2, 2, h // 2, 2, w // 2).permute(0, 1, 3, 5, 2, 4, 6).reshape(b, 8, d // 2, h // 2, w // 2)
+            lll = planes[:, 0]
+            out.append([planes[:, s] for s in range(1, 8)])
+        return [lll] + out[::-1]
+
+    def rec(coeffs):
+        lll = coeffs[0]
+        for bands in coeffs[1:]:
+            lll = lll[:, : bands[0].shape[1], : bands[0].shape[2], : bands[0].shape[3]]
+            p = [lll] + list(bands)
+            halves = [torch.cat([torch.cat([p[q], p[q + 1]], -1), torch.cat([p[q + 2], p[q + 3]], -1)], -2) for q in (0, 4)]
+            lll = torch.cat(halves, -3)
+            for dim in (1, 2, 3):
+                lll = along("synthesis", lll, dim)
+        return lll
+
+    return dec, rec
+
+
+def _stats(times):
+    return {k: dict(min=min(v), median=sorted(v)[len(v) // 2], max=max(v)) for k, v in times.items()}
+
+
+def _timed(legs, repeats):
+    for fn in legs.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(repeats):
+        for k, fn in legs.items():
+            times[k].append(window(fn))
+    return _stats(times)
+
+
+def _forced(fn):
+    def run():
+        _bwt.FORCE_COMPOSED3 = True
+        try:
+            return fn()
+        finally:
+            _bwt.FORCE_COMPOSED3 = False
+    return run
+
+
+def _bricks(fn):
+    """The leg on the brick kernels for every cell of the envelope, whatever ``_bwt.COMPOSED3_CELLS`` routes today."""
+    def run():
+        keep = set(_bwt.COMPOSED3_CELLS)
+        _bwt.COMPOSED3_CELLS.clear()
+        try:
+            return fn()
+        finally:
+            _bwt.COMPOSED3_CELLS.update(keep)
+    return run
+
+
+def _flat3(coeffs):
+    """The tensors of a 3-D coefficient container (dicts or lists of details), in order."""
+    out = []
+    for entry in coeffs:
+        if isinstance(entry, dict):
+            out.extend(entry.values())
+        elif isinstance(entry, (list, tuple)):
+            out.extend(entry)
+        else:
+            out.append(entry)
+    return out
+
+
+def bench3(shape, wavelet, level, repeats):
+    x = torch.randn(*shape, device="cuda", dtype=torch.float32)
+    dec, rec = ptwt_amd.MatrixWavedec3(wavelet, level=level), ptwt_amd.MatrixWaverec3(wavelet)
+    sdec, srec = sparse_legs3(x, wavelet, level)
+    flat = _flat3
+    coeffs = dec(x)
+    flat_c = [coeffs[0]] + [[d[k] for k in ("aad", "ada", "add", "daa", "dad", "dda", "ddd")] for d in coeffs[1:]]
+    err = max(float((a - b).abs().max()) for a, b in zip(flat(coeffs), flat(sdec())))
+    err_rec = float((rec(coeffs) - srec(flat_c)).abs().max())
+    padded_c = ptwt_amd.wavedec3(x, wavelet, level=level, mode="zero")
+    coef_padded = sum(t.numel() for t in flat(padded_c))
+    esz, res = x.element_size(), {}
+    for direction, legs in (("analysis", {"fused": _bricks(lambda: dec(x)), "composed": _forced(lambda: dec(x)),
+                                          "padded": lambda: ptwt_amd.wavedec3(x, wavelet, level=level, mode="zero"), "sparse": sdec}),
+                            ("synthesis", {"fused": _bricks(lambda: rec(coeffs)), "composed": _forced(lambda: rec(coeffs)),
+                                           "padded": lambda: ptwt_amd.waverec3(padded_c, wavelet), "sparse": lambda: srec(flat_c)})):
+        stat = _timed(legs, repeats)
+        byts = {"fused": 2 * x.numel() * esz, "composed": 2 * x.numel() * esz, "padded": (x.numel() + coef_padded) * esz,
+                "sparse": 2 * x.numel() * esz}
+        med = {k: v["median"] for k, v in stat.items()}
+        res[direction] = dict(us=stat, fused_over_composed=med["fused"] / med["composed"], fused_over_padded=med["fused"] / med["padded"],
+                              fused_over_sparse=med["fused"] / med["sparse"],
+                              spread={k: (v["max"] - v["min"]) / v["median"] for k, v in stat.items()},
+                              hbm_share={k: byts[k] / (med[k] * 1e-6) / HBM_PEAK for k in byts})
+    print(json.dumps(dict(shape=list(shape), wavelet=wavelet, level=level, dtype="float32", repeats=repeats,
+                          compulsory_bytes=2 * x.numel() * esz, sparse_vs_fused_max_abs_diff=[err, err_rec], **res)), flush=True)
+
+
+def cells3(repeats):
+    """One level per (direction, dtype, L) cell of the fused 3-D envelope on a 4 x 128^3 volume: fused against composed."""
+    for dtype in (torch.float32, torch.float64):
+        for flen, wavelet in ((2, "haar"), (4, "db2"), (6, "db3"), (8, "db4")):
+            taps = host_taps(wavelet)
+            x = torch.randn(4, 128, 128, 128, device="cuda", dtype=dtype)
+            bands = [torch.randn(4, 64, 64, 64, device="cuda", dtype=dtype) for _ in range(8)]
+            bk_a, bk_s = _bwt.bank(taps, "qr", "analysis"), _bwt.bank(taps, "qr", "synthesis")
+            for direction, fn in ((0, lambda: _bwt.rows_level(x, bk_a, 0)), (1, lambda: _bwt.transposed_level(bands, bk_s, (128, 128, 128)))):
+                stat = _timed({"fused": _bricks(fn), "composed": _forced(fn)}, repeats)  # (the kernel itself, whatever the table says)
+                f, c = stat["fused"], stat["composed"]
+                spread = max(f["max"] - f["min"], c["max"] - c["min"])
+                print(json.dumps(dict(cell=[direction, str(dtype).split(".")[-1], flen], us=stat, fused_over_composed=f["median"] / c["median"],
+                                      spread_us=spread, route="fused" if c["median"] - f["median"] > spread else "composed",
+                                      hbm_share_fused=2 * x.numel() * x.element_size() / (f["median"] * 1e-6) / HBM_PEAK)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--shape", choices=["2d", "1d", "both"], default="both")
+    ap.add_argument("--shape", choices=["2d", "1d", "both", "3d", "cells"], default="both")
     args = ap.parse_args()
     _engine.set_option(_engine.OPT_PYRAMID_MODE, 2)
     _engine.set_option(_engine.OPT_PAIR_MODE, 2)
@@ -129,6 +276,11 @@ def main():
         bench((64, 1024, 1024), "db4", 3, args.repeats)
     if args.shape in ("1d", "both"):
         bench((32, 1000000), "db5", 10, args.repeats)
+    if args.shape == "3d":
+        bench3((8, 256, 256, 256), "db2", 3, args.repeats)
+        bench3((32, 100, 100, 100), "db4", 2, args.repeats)
+    if args.shape == "cells":
+        cells3(args.repeats)
 
 
 if __name__ == "__main__":
