@@ -384,6 +384,27 @@ int mifwt_bwt3_fwd(const mifwt_level_desc* desc, const void* x, void* approx, vo
 int mifwt_bwt3_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* lo, const double* hi,
                    const mifwt_bwt_tables* tables, void* stream);
 
+/* A SUBTREE of a 1-D boundary-wavelet PACKET tree per launch (kernel ids 32 / 33, csrc/mifwt_bwt_tree.hip; ptwt.WaveletPacket with
+ * mode="boundary").  A packet node of h samples splits into two nodes of h / 2, so level s below a row of n samples is the dense span
+ * [2^s nodes][n / 2^s] of again n numbers.  One workgroup keeps a row and its next level in LDS and computes `nlevels` levels.
+ *   rows, n     the rows (nodes of the tree folded into the batch) and their length
+ *   levels      HOST array of `nlevels` DEVICE pointers to dense [rows, n] buffers.  mifwt_bwt_tree_fwd: levels[i] = level i + 1 below the
+ *               rows (written).  mifwt_bwt_tree_inv: levels[i] = level i, levels[0] the rows themselves (all written; `leaves` = level
+ *               nlevels, dense [rows, n], read).
+ *   x           rows of unit sample stride, `x_row_stride` >= n elements apart
+ *   lo / hi / tables   as for mifwt_bwt_fwd (dec_* and the analysis tables) / mifwt_bwt_inv (rec_* and the synthesis tables)
+ * mifwt_bwt_tree_levels: how many consecutive levels ONE launch takes from a node of n samples, at most `max_levels` (0: none; a host
+ * decision, no device needed).  Envelope: f32 / f64, even L <= 20, at least two levels, every fused level's input node even and at least
+ * 2 (L-1) samples long, n <= 8192 f32 / 4096 f64 samples (two LDS images of 32 KB).  The calls take exactly what that function answers
+ * for (n, nlevels); MIFWT_ERR_UNSUPPORTED otherwise (odd n, L > 20, nlevels < 2, f16, ...), nothing launched. */
+#define MIFWT_KID_BWT_TREE_FWD 32
+#define MIFWT_KID_BWT_TREE_INV 33
+int mifwt_bwt_tree_levels(int dtype, int filt_len, int64_t n, int max_levels);
+int mifwt_bwt_tree_fwd(int dtype, int filt_len, int64_t rows, int64_t n, int64_t x_row_stride, int nlevels, const void* x,
+                       void* const* levels, const double* lo, const double* hi, const mifwt_bwt_tables* tables, void* stream);
+int mifwt_bwt_tree_inv(int dtype, int filt_len, int64_t rows, int64_t n, int nlevels, const void* leaves, void* const* levels,
+                       const double* lo, const double* hi, const mifwt_bwt_tables* tables, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -439,7 +460,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   26 / 27  fused boundary-wavelet analysis / synthesis level, 1-D and 2-D (mifwt_bwt_fwd / mifwt_bwt_inv; answered by mifwt_bwt_kernel_id)
  *   28 / 29  one axis of a boundary-wavelet level through a run-time tap loop (mifwt_bwt_axis_fwd / mifwt_bwt_axis_inv)
  *   30 / 31  fused 3-D boundary-wavelet analysis / synthesis level, LDS bricks (mifwt_bwt3_fwd / mifwt_bwt3_inv; f32 / f64, even L <= 8;
- *          answered by mifwt_bwt3_kernel_id) */
+ *          answered by mifwt_bwt3_kernel_id)
+ *   32 / 33  a subtree (two or more levels) of a 1-D boundary-wavelet packet tree per launch, analysis / synthesis, one row per workgroup
+ *          (mifwt_bwt_tree_fwd / mifwt_bwt_tree_inv; f32 / f64, even L <= 20; answered by mifwt_bwt_tree_levels) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

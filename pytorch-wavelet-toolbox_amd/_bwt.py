@@ -11,6 +11,11 @@ samples; longer filters run one generic launch per axis (28 / 29); a level with 
 samples — is a dense ``torch.matmul`` with the small level matrix.  Three transformed axes have kernels of their own (ids 30 / 31,
 csrc/mifwt_bwt3.hip: even ``L <= 8``); what they decline runs the axis passes width, height, depth — seven launches per level.  The tables are cached per bank and uploaded once per device;
 after that a call allocates its outputs and enqueues launches, nothing else: no host round trip, capturable.
+
+Packet trees (``packets.py``, ``mode="boundary"``) expand whole levels: ``rows_tree`` / ``transposed_tree`` compute two or more consecutive
+levels of a 1-D tree in ONE launch (ids 32 / 33, csrc/mifwt_bwt_tree.hip: a row and its next level stay in LDS); ``tree_route`` splits a
+range of levels into such runs and per-level launches.  No autograd: a tree that wants gradients runs level by level through ``rows`` /
+``transposed``.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ from . import _boundary, _engine
 
 KID_FWD, KID_INV, KID_AXIS_FWD, KID_AXIS_INV = 26, 27, 28, 29
 KID_FWD3, KID_INV3 = 30, 31
+KID_TREE_FWD, KID_TREE_INV = 32, 33
 
 _ZERO, _REFLECT = _engine.MODE_IDS["zero"], _engine.MODE_IDS["reflect"]
 
@@ -34,6 +40,15 @@ FORCE_COMPOSED3 = False
 # more than the spread of its windows (EXPERIMENTS.md part B).  The synthesis bricks for 6 and 8 taps hold a CU alone (100 - 150 KB of
 # LDS, csrc/mifwt_bwt3.hip) and have no such measurement: they are routed to the axis passes.
 COMPOSED3_CELLS: Set[Tuple[int, torch.dtype, int]] = {(1, dt, flen) for dt in (torch.float32, torch.float64) for flen in (6, 8)}
+
+
+# Tests and tools/boundary_bench.py set this to run a packet tree on per-level launches although a subtree launch (ids 32 / 33) would take it.
+FORCE_PER_LEVEL_TREE = False
+# (direction, dtype) cells of the subtree envelope that stay on per-level launches all the same (direction 0 analysis, 1 synthesis): the rule of
+# COMPOSED3_CELLS — a cell is on the subtree kernels only where `tools/boundary_bench.py --shape packets` has shown their median ahead of the
+# per-level one by more than the spread of its windows (EXPERIMENTS.md part B).  No cell has such a measurement yet: all four are listed, the
+# subtree kernels run where a caller (the tests, the benchmark tool) empties this set.
+PER_LEVEL_TREE_CELLS: Set[Tuple[int, torch.dtype]] = {(d, dt) for d in (0, 1) for dt in (torch.float32, torch.float64)}
 
 
 def _composed3(direction: int, dtype: torch.dtype, flen: int) -> bool:
@@ -71,6 +86,12 @@ def _lib():
         lib.mifwt_bwt_axis_fwd.argtypes = [ci, ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
         lib.mifwt_bwt_axis_inv.restype = ci
         lib.mifwt_bwt_axis_inv.argtypes = [ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
+        lib.mifwt_bwt_tree_levels.restype = ci
+        lib.mifwt_bwt_tree_levels.argtypes = [ci, ci, i64, ci]
+        lib.mifwt_bwt_tree_fwd.restype = ci
+        lib.mifwt_bwt_tree_fwd.argtypes = [ci, ci, i64, i64, i64, ci, vp, vpp, dbl_p, dbl_p, tab_p, vp]
+        lib.mifwt_bwt_tree_inv.restype = ci
+        lib.mifwt_bwt_tree_inv.argtypes = [ci, ci, i64, i64, ci, vp, vpp, dbl_p, dbl_p, tab_p, vp]
         _bound = True
     return lib
 
@@ -321,6 +342,96 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
     else:
         raise NotImplementedError("boundary-wavelet levels exist for one, two and three transformed axes")
     return y
+
+
+# ---- packet trees: a run of levels per launch (no autograd) ---------------------------------------------------------------------------------
+_tree_levels: dict = {}
+_engine._routing_caches.append(_tree_levels)
+
+
+def tree_levels(dtype: torch.dtype, flen: int, n: int, max_levels: int) -> int:
+    """How many consecutive levels ONE subtree launch takes from a node of ``n`` samples (0: none) — ``mifwt_bwt_tree_levels``, cached."""
+    key = (dtype, flen, n, max_levels)
+    k = _tree_levels.get(key)
+    if k is None:
+        dt = _engine._DTYPE_IDS.get(dtype, -1)
+        k = _tree_levels[key] = int(_lib().mifwt_bwt_tree_levels(dt, flen, n, max_levels)) if dt >= 0 and max_levels >= 2 else 0
+    return k
+
+
+def tree_route(n: int, flen: int, dtype: torch.dtype, first: int, last: int, assigned: Sequence[int] = (), direction: int = 0,
+               node_len: Optional[int] = None) -> List[Tuple[int, int]]:
+    """Split the expansion of levels ``first`` .. ``last`` of a 1-D packet tree over a root of ``n`` samples (``last`` > ``first``: the
+    deepest level produced) into launches: a list of (input level, number of levels); 1 = a per-level launch, >= 2 = one subtree launch.
+    A node of ``h`` samples has children of ``ceil(h / 2)``.  A level outside the subtree envelope (node too long, odd, short) is a
+    per-level launch, every maximal run of at least two levels inside it one subtree launch; a run does not go past a level listed in
+    ``assigned`` (levels that hold nodes set by the user: they are gathered before they are expanded), which may only be its input or
+    its last output.  ``node_len``: the node length at ``first`` where it is not the one the root implies.  Pure: no device, no tensors."""
+    h = n
+    for _ in range(first):
+        h = (h + 1) // 2
+    if node_len is not None:
+        h = node_len
+    fused = not FORCE_PER_LEVEL_TREE and (direction, dtype) not in PER_LEVEL_TREE_CELLS
+    steps: List[Tuple[int, int]] = []
+    s = first
+    while s < last:
+        stop = min([last] + [t for t in assigned if t > s])
+        k = tree_levels(dtype, flen, h, stop - s) if fused and stop - s >= 2 else 0
+        if k < 2:
+            k = 1
+        steps.append((s, k))
+        for _ in range(k):
+            h = (h + 1) // 2
+        s += k
+    return steps
+
+
+def tree_route_up(m: int, flen: int, dtype: torch.dtype, kmax: int, direction: int = 1) -> int:
+    """Synthesis counterpart of :func:`tree_route`: from leaves of ``m`` samples whose ``kmax`` levels above double exactly, how many
+    levels the next launch rebuilds — the longest subtree run (>= 2) inside the envelope, else 1."""
+    if FORCE_PER_LEVEL_TREE or (direction, dtype) in PER_LEVEL_TREE_CELLS:
+        return 1
+    for k in range(kmax, 1, -1):
+        if tree_levels(dtype, flen, m << k, k) == k:
+            return k
+    return 1
+
+
+def rows_tree(x: torch.Tensor, bk: Bank, k: int) -> List[torch.Tensor]:
+    """``k`` >= 2 analysis levels of a packet tree below every row of x [R, n] in one launch (id 32): the list of the level buffers
+    [R, 2^i, n / 2^i], i = 1 .. k (node order = natural order of the paths).  (n, k) must be inside ``tree_levels``."""
+    _engine._require_gpu(x)
+    x = _unit_last(x)
+    r, n = int(x.shape[0]), int(x.shape[1])
+    if r > 1 and x.stride(0) < n:
+        x = x.contiguous()
+    out = [torch.empty((r, n), dtype=x.dtype, device=x.device) for _ in range(k)]
+    if r:
+        dt = _engine._DTYPE_IDS[x.dtype]
+        ptrs = _engine._arr(ctypes.c_void_p, k)(*[t.data_ptr() for t in out])
+        lib, tab, xp, xs = _lib(), bk.tables(x.device), x.data_ptr(), x.stride(0) if r > 1 else n
+        lo, hi, L = _engine._taps_array(bk.f_lo), _engine._taps_array(bk.f_hi), bk.filt_len
+        _launch(0, KID_TREE_FWD, (n,), x, lambda stream: lib.mifwt_bwt_tree_fwd(dt, L, r, n, xs, k, xp, ptrs, lo, hi, ctypes.byref(tab), stream))
+    return [out[i].view(r, 1 << (i + 1), n >> (i + 1)) for i in range(k)]
+
+
+def transposed_tree(leaves: torch.Tensor, bk: Bank, k: int) -> List[torch.Tensor]:
+    """``k`` >= 2 synthesis levels in one launch (id 33): leaves [R, 2^k, n / 2^k] -> the list of the level buffers [R, 2^i, n / 2^i],
+    i = 0 .. k - 1 (entry 0 = the rebuilt rows [R, 1, n])."""
+    _engine._require_gpu(leaves)
+    leaves = leaves.contiguous()
+    r = int(leaves.shape[0])
+    n = int(leaves.shape[1] * leaves.shape[2])
+    out = [torch.empty((r, n), dtype=leaves.dtype, device=leaves.device) for _ in range(k)]
+    if r:
+        dt = _engine._DTYPE_IDS[leaves.dtype]
+        ptrs = _engine._arr(ctypes.c_void_p, k)(*[t.data_ptr() for t in out])
+        lib, tab, lp = _lib(), bk.tables(leaves.device), leaves.data_ptr()
+        # (the C entry takes the filters in rec order and reverses them into row filters)
+        lo, hi, L = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi), bk.filt_len
+        _launch(1, KID_TREE_INV, (n,), leaves, lambda stream: lib.mifwt_bwt_tree_inv(dt, L, r, n, k, lp, ptrs, lo, hi, ctypes.byref(tab), stream))
+    return [out[i].view(r, 1 << i, n >> i) for i in range(k)]
 
 
 # ---- short levels: dense matrices, plain torch (differentiable as it stands, no host synchronisation) ----------------------------

@@ -10,7 +10,19 @@ MI355X-first restatement: a packet level is ONE engine launch.  All nodes of a l
 ``[batch * nb^s, nb, M..]`` IS that layout for s + 1, no copies — and a node is a strided view of it.  A miss on a
 key therefore expands whole levels down to the requested depth (s launches for depth s).  Nodes assigned by the
 user are honoured: a level that contains assigned nodes is re-gathered before it is expanded or reconstructed
-from.  The sparse-matrix ``mode="boundary"`` backend is out of scope of this engine.
+from.
+
+``mode="boundary"`` (reference src/ptwt/packets.py:240-271, :541-590: one ``MatrixWavedec(level=1)`` resp. separable
+``MatrixWavedec2(level=1)`` per node) expands a node by one padding-free boundary-wavelet level, ``odd_coeff_padding_mode="zero"``: a
+node of n samples gives children of ceil(n / 2), so the level buffers are exactly those above and a level is one launch of the
+boundary kernels (``_bwt.rows`` / ``_bwt.transposed``, ids 26 / 27) over all its nodes.  In 1-D every level of the tree below one
+input row is again one contiguous span of the row's length, and a run of two or more levels is ONE launch of the subtree kernels
+(ids 32 / 33, csrc/mifwt_bwt_tree.hip) wherever ``_bwt.tree_route`` finds it inside their envelope and ``_bwt.PER_LEVEL_TREE_CELLS``
+lets it (a table filled by measurement; today it keeps every cell on per-level launches).  A tree whose input (or, in
+``reconstruct``, whose leaves) requires grad always runs level by level through the differentiable level maps.  ``reconstruct``
+crops an inner node that comes out one sample long, not the root: an input of 67 samples comes back with 68, as in the reference.
+Both ``orthogonalization`` values give the boundary filters in their Gram-Schmidt sign (``matmul_transform.py``); the filter bank is
+read once, on the host, when the object is built; float32 / float64 tensors on a ROCm device.
 """
 from __future__ import annotations
 
@@ -20,10 +32,25 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _engine, _fwt
+from . import _bwt, _engine, _fwt
 from ._wavelets import as_wavelet, dwt_max_level, filter_length, host_taps
+from .matmul_transform import _bank_taps
+from .matmul_transform_2 import _NON_SEPARABLE
 
 __all__ = ["WaveletPacket", "WaveletPacket2D"]
+
+# mode="boundary": the device check and the level maps, looked up here at call time (CPU tests substitute the float64 host operators)
+_BOUNDARY_DEVICE = "mode='boundary' is implemented for tensors on a ROCm device only"
+
+
+def _boundary_on_device(t: torch.Tensor) -> bool:
+    return t.is_cuda
+
+
+_boundary_rows = _bwt.rows                      # (x [R, n..], bank, mode id) -> [R, 2^d, M..]
+_boundary_transposed = _bwt.transposed          # (bands, bank, out extents) -> [R, n..]
+_boundary_rows_tree = _bwt.rows_tree            # (x [R, n], bank, k) -> k level buffers
+_boundary_transposed_tree = _bwt.transposed_tree
 
 
 def _graycode(level: int, lo: str, hi: str) -> List[str]:
@@ -52,11 +79,12 @@ class _PacketTree(collections.UserDict):
         super().__init__()
         self.wavelet = as_wavelet(wavelet)
         self.mode = mode
+        self._banks = None
         if mode == "boundary":
-            raise NotImplementedError(
-                "mode='boundary' selects the reference's sparse-matrix backend (src/ptwt/matmul_transform*.py), which is "
-                "outside this engine's scope; use a padding mode."
-            )
+            taps = _bank_taps(self.wavelet, self.orthogonalization)
+            if self._ndim == 2 and not self.separable:
+                raise NotImplementedError(_NON_SEPARABLE)
+            self._banks = tuple(_bwt.bank(taps, self.orthogonalization, which) for which in ("analysis", "synthesis"))
         self._axes = _fwt._ensure_axes(axes, self._ndim)
         self._filter_keys = set(self._bands)
         self.maxlevel: Optional[int] = None
@@ -69,6 +97,11 @@ class _PacketTree(collections.UserDict):
     # ---- construction -------------------------------------------------------------------------------------
     def transform(self, data: torch.Tensor, maxlevel: Optional[int] = None):
         """(Re)initialise the tree lazily with ``data`` (src/ptwt/packets.py:149-177, :436-467)."""
+        if self._banks is not None:
+            if not _boundary_on_device(data):
+                raise NotImplementedError(_BOUNDARY_DEVICE)
+            if data.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"Input dtype {data.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
         self.data = {}
         self._assigned = set()
         self._layout = _fwt._Layout(data, self._ndim, self._axes)
@@ -127,13 +160,40 @@ class _PacketTree(collections.UserDict):
             out = _fwt._AnalysisLevel.apply(flat, dec_lo, dec_hi, mode_id, *((tap_t[0], tap_t[1]) if tap_t else (None, None)))
         else:
             out = _engine.ENGINE.analysis(flat, dec_lo, dec_hi, mode_id)  # [B * nb^level, nb, M..]
-        nxt = out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:])
-        while len(self._levels) <= level + 1:
+        self._store_level(level + 1, out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:]))
+
+    def _store_level(self, level: int, buf: torch.Tensor) -> None:
+        while len(self._levels) <= level:
             self._levels.append(None)
-        self._levels[level + 1] = nxt
-        for key in self._keys_of_level(level + 1):
+        self._levels[level] = buf
+        for key in self._keys_of_level(level):
             if key not in self._assigned:
-                self.data[key] = self._node_view(nxt, key)
+                self.data[key] = self._node_view(buf, key)
+
+    def _expand_boundary(self, first: int, last: int) -> None:
+        """Levels ``first + 1 .. last`` from level ``first`` with the boundary-wavelet level maps: one launch per level, in 1-D one
+        subtree launch per run of levels that ``_bwt.tree_route`` finds inside the subtree kernels' envelope (never when a gradient
+        is wanted; never past a level that holds nodes assigned by the user, which are gathered first)."""
+        bank, flen, nb = self._banks[0], self._banks[0].filt_len, len(self._bands)
+        zero = _engine.MODE_IDS["zero"]
+        level = first
+        while level < last:
+            src = self._level_buffer(level)
+            flat = src.reshape(-1, *src.shape[1 + level:])
+            if min(flat.shape[1:]) < flen:
+                raise ValueError(f"A node of extents {tuple(flat.shape[1:])} at level {level} is shorter than the filter ({flen} taps) "
+                                 f"and cannot be expanded; choose a smaller maxlevel.")
+            k = 1
+            if self._ndim == 1 and not (torch.is_grad_enabled() and flat.requires_grad):
+                held = sorted({len(key) for key in self._assigned if level < len(key) <= last})
+                k = _bwt.tree_route(int(flat.shape[1]), flen, flat.dtype, level, last, held, 0, node_len=int(flat.shape[1]))[0][1]
+            if k >= 2:
+                for i, buf in enumerate(_boundary_rows_tree(flat, bank, k)):
+                    self._store_level(level + 1 + i, buf.reshape(src.shape[0], *([nb] * (level + 1 + i)), buf.shape[-1]))
+            else:
+                out = _boundary_rows(flat, bank, zero)
+                self._store_level(level + 1, out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:]))
+            level += k
 
     # ---- dict protocol ----------------------------------------------------------------------------------------
     def __setitem__(self, key: str, value: torch.Tensor) -> None:
@@ -165,8 +225,11 @@ class _PacketTree(collections.UserDict):
             start = len(key) - 1
             while start > 0 and not all(k in self.data for k in self._keys_of_level(start)):
                 start -= 1
-            for level in range(start, len(key)):
-                self._expand_level(level)
+            if self._banks is not None:
+                self._expand_boundary(start, len(key))
+            else:
+                for level in range(start, len(key)):
+                    self._expand_level(level)
         return self.data[key]
 
     # ---- synthesis ----------------------------------------------------------------------------------------------
@@ -176,6 +239,8 @@ class _PacketTree(collections.UserDict):
         if self.maxlevel is None:
             root = self[""]  # raises the reference's ValueError for an uninitialised tree
             self.maxlevel = dwt_max_level(min(self._layout.fold(root).shape[1:]), filter_length(self.wavelet))
+        if self._banks is not None:
+            return self._reconstruct_boundary()
         _, _, rec_lo, rec_hi = host_taps(self.wavelet)
         tap_t = _fwt._tap_tensors(self.wavelet)
         flen = len(rec_lo)
@@ -211,6 +276,61 @@ class _PacketTree(collections.UserDict):
                 self.data[key] = self._node_view(buf, key)
         return self
 
+    def _require_children(self, level: int) -> None:
+        for node in self._keys_of_level(level):
+            for child in self._bands:
+                if node + child not in self.data:
+                    raise KeyError(f"Key {node + child} not found")
+
+    def _extents_of_level(self, level: int):
+        """Transformed extents of the nodes of ``level`` as the tree holds them (None: the level has no node yet)."""
+        key = self._keys_of_level(level)[0]
+        return tuple(self._layout.fold(self.data[key]).shape[1:]) if key in self.data else None
+
+    def _reconstruct_boundary(self):
+        """``reconstruct`` with the transposed boundary-wavelet level maps; a node that comes out one sample long is cropped to the
+        extents it had, the root is not.  1-D, no gradient wanted: runs of levels that double exactly go through one subtree launch."""
+        bank, nb, nd = self._banks[1], len(self._bands), self._ndim
+        level = self.maxlevel
+        while level > 0:
+            self._require_children(level - 1)
+            children = self._level_buffer(level)  # [B, nb^level.., M..]
+            k = 1
+            if nd == 1 and not (torch.is_grad_enabled() and children.requires_grad):
+                # levels above that are exactly twice as long as the one below them: the levels the analysis finds even.  (A root of odd
+                # length comes back one sample longer, uncropped, from the per-level launch.)
+                m, up = int(children.shape[-1]), 0
+                while up < level:
+                    ext = self._extents_of_level(level - up - 1)
+                    if ext is None or ext[0] != m << (up + 1):
+                        break
+                    up += 1
+                k = _bwt.tree_route_up(m, bank.filt_len, children.dtype, up)
+            if k >= 2:
+                leaves = children.reshape(-1, 1 << k, children.shape[-1])
+                for i, buf in enumerate(_boundary_transposed_tree(leaves, bank, k)):
+                    self._replace_level(level - k + i, buf.reshape(children.shape[0], *([nb] * (level - k + i)), buf.shape[-1]))
+            else:
+                flat = children.reshape(-1, nb, *children.shape[1 + level:])
+                out_ext = [2 * int(c) for c in flat.shape[2:]]
+                target = self._extents_of_level(level - 1) if level > 1 else None
+                if target is None and level > 1:
+                    target = self._layout.fold(self[self._keys_of_level(level - 1)[0]]).shape[1:]
+                if target is not None:
+                    for a in range(nd):
+                        if out_ext[a] != target[a]:
+                            assert out_ext[a] == target[a] + 1, "padding error, please open an issue on github"
+                            out_ext[a] = int(target[a])
+                rec = _boundary_transposed([flat[:, s] for s in range(nb)], bank, tuple(out_ext))
+                self._replace_level(level - 1, rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:]))
+            level -= k
+        return self
+
+    def _replace_level(self, level: int, buf: torch.Tensor) -> None:
+        for key in self._keys_of_level(level):
+            self._assigned.discard(key)
+        self._store_level(level, buf)
+
 
 class WaveletPacket(_PacketTree):
     """One-dimensional wavelet packet tree (drop-in for ``ptwt.WaveletPacket``, src/ptwt/packets.py:67-360)."""
@@ -241,7 +361,11 @@ class WaveletPacket2D(_PacketTree):
 
     Key chars: ``a`` approximation, ``h`` / ``v`` / ``d`` the (H, V, D) details of ``wavedec2`` — i.e. engine bands
     ``da`` / ``ad`` / ``dd``.  With ``separable=True`` the reference routes through ``fswavedec2`` and maps its
-    ``"ad"`` band to ``h`` and ``"da"`` to ``v`` (src/ptwt/packets.py:592-620); the same mapping is kept here."""
+    ``"ad"`` band to ``h`` and ``"da"`` to ``v`` (src/ptwt/packets.py:592-620); the same mapping is kept here.
+
+    ``mode="boundary"`` needs ``separable=True`` (keys ``a, h, v, d`` = ``ll`` and the three details in the order of
+    ``MatrixWavedec2(level=1, separable=True)``).  With ``separable=False`` — the class default — it raises ``NotImplementedError``:
+    the non-separable boundary transform orthogonalises the rows of a 2-D Kronecker matrix, a different transform that is not built."""
 
     _ndim = 2
     _bands = {"a": 0, "h": 2, "v": 1, "d": 3}

@@ -16,7 +16,12 @@ with the fused leg in the same process), wavedec3 / waverec3 with mode="zero", a
 ``_bwt.COMPOSED3_CELLS`` is filled from its verdicts (fused only where its median beats the composed median by more than the spread of
 the windows).
 
-    python tools/boundary_bench.py [--repeats 5] [--shape 2d|1d|3d|cells]
+--shape packets: WaveletPacket(mode="boundary") — the whole tree of a depth (analysis) and reconstruct() from its leaves (synthesis) on
+the default subtree route (kernel ids 32 / 33 where ``_bwt.tree_route`` takes them), on per-level launches of the same library
+(``_bwt.FORCE_PER_LEVEL_TREE``, alternating in the same process) and WaveletPacket(mode="zero") of the same depth; the verdict per
+(direction, dtype) cell fills ``_bwt.PER_LEVEL_TREE_CELLS`` by the rule of the 3-D cells.
+
+    python tools/boundary_bench.py [--repeats 5] [--shape 2d|1d|3d|cells|packets]
 """
 import argparse
 import json
@@ -265,10 +270,60 @@ def cells3(repeats):
                                       hbm_share_fused=2 * x.numel() * x.element_size() / (f["median"] * 1e-6) / HBM_PEAK)), flush=True)
 
 
+def _per_level(fn):
+    def run():
+        _bwt.FORCE_PER_LEVEL_TREE = True
+        try:
+            return fn()
+        finally:
+            _bwt.FORCE_PER_LEVEL_TREE = False
+    return run
+
+
+def _subtree(fn):
+    """The leg on the subtree kernels wherever the envelope allows, whatever ``_bwt.PER_LEVEL_TREE_CELLS`` routes today."""
+    def run():
+        keep = set(_bwt.PER_LEVEL_TREE_CELLS)
+        _bwt.PER_LEVEL_TREE_CELLS.clear()
+        try:
+            return fn()
+        finally:
+            _bwt.PER_LEVEL_TREE_CELLS.update(keep)
+    return run
+
+
+def bench_packets(shape, wavelet, depth, dtype, repeats):
+    x = torch.randn(*shape, device="cuda", dtype=dtype)
+    leaf = "a" * depth
+
+    def tree(mode):
+        wp = ptwt_amd.WaveletPacket(x, wavelet, mode=mode, maxlevel=depth)
+        wp[leaf]
+        return wp
+
+    grown = {"fused": _subtree(lambda: tree("boundary"))(), "per_level": _per_level(lambda: tree("boundary"))(), "padded": tree("zero")}
+    keys = ptwt_amd.WaveletPacket.get_level(depth, "natural")
+    err = max(float((grown["fused"][k] - grown["per_level"][k]).abs().max()) for k in keys)
+    res = {}
+    for direction, legs in (("analysis", {"fused": _subtree(lambda: tree("boundary")), "per_level": _per_level(lambda: tree("boundary")),
+                                          "padded": lambda: tree("zero")}),
+                            ("synthesis", {"fused": _subtree(grown["fused"].reconstruct), "per_level": _per_level(grown["per_level"].reconstruct),
+                                           "padded": grown["padded"].reconstruct})):
+        stat = _timed(legs, repeats)
+        f, c = stat["fused"], stat["per_level"]
+        spread = max(f["max"] - f["min"], c["max"] - c["min"])
+        byts = (1 + depth) * x.numel() * x.element_size()  # the input (the leaves) once, every level written once
+        res[direction] = dict(us=stat, fused_over_per_level=f["median"] / c["median"], fused_over_padded=f["median"] / stat["padded"]["median"],
+                              spread_us=spread, route="subtree" if c["median"] - f["median"] > spread else "per_level",
+                              hbm_share_fused=byts / (f["median"] * 1e-6) / HBM_PEAK)
+    print(json.dumps(dict(shape=list(shape), wavelet=wavelet, depth=depth, dtype=str(dtype).split(".")[-1], repeats=repeats,
+                          fused_vs_per_level_max_abs_diff=err, **res)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--shape", choices=["2d", "1d", "both", "3d", "cells"], default="both")
+    ap.add_argument("--shape", choices=["2d", "1d", "both", "3d", "cells", "packets"], default="both")
     args = ap.parse_args()
     _engine.set_option(_engine.OPT_PYRAMID_MODE, 2)
     _engine.set_option(_engine.OPT_PAIR_MODE, 2)
@@ -281,6 +336,10 @@ def main():
         bench3((32, 100, 100, 100), "db4", 2, args.repeats)
     if args.shape == "cells":
         cells3(args.repeats)
+    if args.shape == "packets":
+        bench_packets((4096, 4096), "db4", 6, torch.float32, args.repeats)
+        bench_packets((32, 1024), "db4", 6, torch.float32, args.repeats)
+        bench_packets((4096, 4096), "db4", 6, torch.float64, args.repeats)
 
 
 if __name__ == "__main__":
