@@ -599,6 +599,8 @@ class HipLevelEngine:
 
         self._run(p, 0, x, call)
         if rc_box and rc_box[0] == -2:
+            if level_events:  # (nothing was launched: the recorded event would claim a kernel that did not run)
+                level_events.pop()
             return None
         return bufs
 
@@ -686,6 +688,8 @@ class HipLevelEngine:
 
         self._run(p, 1, approx, call)
         if rc_box and rc_box[0] == -2:
+            if level_events:  # (nothing was launched, see analysis_tail)
+                level_events.pop()
             return None
         return y
 
