@@ -191,8 +191,33 @@ def _axis_strides(t: torch.Tensor):
 
 
 def _outer_axis_inner(t: torch.Tensor, axis: int) -> torch.Tensor:
-    """A dense [B, d0, d1, d2] tensor as the [outer, n, inner] view whose middle axis is ``axis`` (1 .. 3)."""
+    """A [B, d0(, d1(, d2))] tensor as the [outer, n, inner] view whose middle axis is ``axis`` (1 .. 3)."""
     return t.reshape(int(np.prod(t.shape[:axis])), t.shape[axis], int(np.prod(t.shape[axis + 1:])))
+
+
+def _route(direction: int, key, ndim: int, dtype: torch.dtype, flen: int, desc):
+    """(reference to the level descriptor, kernel id) of a level; -2: no fused kernel takes it, it runs the composed axis passes.
+    The descriptor ``desc()`` builds and the kernel's answer are cached under ``key``."""
+    p = _plans.get(key)
+    if p is None:
+        lib, d = _lib(), desc()
+        kid = (lib.mifwt_bwt3_kernel_id if ndim == 3 else lib.mifwt_bwt_kernel_id)(ctypes.byref(d), direction)
+        if kid < 0 and kid != -2:
+            _engine._check(kid)
+        p = _plans[key] = (d, ctypes.byref(d), kid)
+    _, ref, kid = p
+    if kid == (KID_FWD3, KID_INV3)[direction] and _composed3(direction, dtype, flen):
+        kid = -2
+    return ref, kid
+
+
+def _composed_setup(t: torch.Tensor, ndim: int):
+    """What the composed axis passes need before their first launch: the dtype id, and the refusals."""
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"Input dtype {t.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
+    if ndim > 3:
+        raise NotImplementedError("boundary-wavelet levels exist for one, two and three transformed axes")
+    return _engine._DTYPE_IDS[t.dtype]
 
 
 # ---- the two level maps (no autograd) ---------------------------------------------------------------------------------------------
@@ -209,64 +234,41 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
     if is_short(sig, L):
         return _rows_dense(x, bk, mode_id)
     x = _unit_last(x)
-    buf = torch.empty((x.shape[0], 1 << ndim, *coef), dtype=x.dtype, device=x.device)
+    b = x.shape[0]
+    buf = torch.empty((b, 1 << ndim, *coef), dtype=x.dtype, device=x.device)
     if buf.numel() == 0:
         return buf
     lib = _lib()
-    key = (0, x.shape, x.stride(), x.dtype, mode_id, L)
-    p = _plans.get(key)
-    if p is None:
-        bs = list(buf.stride())
-        st = [bs[0]] + bs[2:]
-        d = _desc(ndim, x.dtype, mode_id, L, x.shape[0], sig, x.stride(), coef, st, st)
-        kid = (lib.mifwt_bwt3_kernel_id if ndim == 3 else lib.mifwt_bwt_kernel_id)(ctypes.byref(d), 0)
-        if kid < 0 and kid != -2:
-            _engine._check(kid)
-        p = _plans[key] = (d, ctypes.byref(d), kid, bs[1] * x.element_size())
-    d, ref, kid, plane = p
-    if kid == KID_FWD3 and _composed3(0, x.dtype, L):
-        kid = -2
+    st = [buf.stride(0), *buf.stride()[2:]]
+    ref, kid = _route(0, (0, x.shape, x.stride(), x.dtype, mode_id, L), ndim, x.dtype, L,
+                      lambda: _desc(ndim, x.dtype, mode_id, L, b, sig, x.stride(), coef, st, st))
     tab = bk.tables(x.device)
     lo, hi = _engine._taps_array(bk.f_lo), _engine._taps_array(bk.f_hi)
     if kid in (KID_FWD, KID_FWD3):
         base, xp = buf.data_ptr(), x.data_ptr()
-        ptrs = _engine._band_ptrs(base, plane, (1 << ndim) - 1)
+        ptrs = _engine._band_ptrs(base, buf.stride(1) * x.element_size(), (1 << ndim) - 1)
         entry = lib.mifwt_bwt3_fwd if kid == KID_FWD3 else lib.mifwt_bwt_fwd
         _launch(0, kid, sig, x, lambda stream: entry(ref, xp, base, ptrs, lo, hi, ctypes.byref(tab), stream))
         return buf
-    if x.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"Input dtype {x.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
-    dt = _engine._DTYPE_IDS[x.dtype]
-
-    def axis_fwd(src, n, outer, inner, out_lo, out_hi, mode):
-        _launch(0, KID_AXIS_FWD, (n,), src, lambda stream: lib.mifwt_bwt_axis_fwd(
-            dt, L, mode, outer, n, inner, src.data_ptr(), _axis_strides(src), out_lo.data_ptr(), _axis_strides(out_lo), out_hi.data_ptr(),
-            _axis_strides(out_hi), lo, hi, ctypes.byref(tab), stream))
-
-    if ndim == 1:
-        axis_fwd(x.unsqueeze(-1), sig[0], x.shape[0], 1, buf[:, 0].unsqueeze(-1), buf[:, 1].unsqueeze(-1), mode_id)
-    elif ndim == 2:
+    dt = _composed_setup(x, ndim)
+    if ndim > 1:
         x = x.contiguous()
-        b, n0, n1 = x.shape
-        tmp = torch.empty((2, b, n0, coef[1]), dtype=x.dtype, device=x.device)
-        axis_fwd(x.reshape(b * n0, n1, 1), n1, b * n0, 1, tmp[0].reshape(b * n0, coef[1], 1), tmp[1].reshape(b * n0, coef[1], 1), mode_id)
-        axis_fwd(tmp[0], n0, b, coef[1], buf[:, 0], buf[:, 2], mode_id)
-        axis_fwd(tmp[1], n0, b, coef[1], buf[:, 1], buf[:, 3], mode_id)
-    elif ndim == 3:
-        # width, height, depth: 1 + 2 + 4 launches
-        x = x.contiguous()
-        b, n0, n1, n2 = x.shape
-        t_w = torch.empty((2, b, n0, n1, coef[2]), dtype=x.dtype, device=x.device)
-        axis_fwd(_outer_axis_inner(x, 3), n2, b * n0 * n1, 1, _outer_axis_inner(t_w[0], 3), _outer_axis_inner(t_w[1], 3), mode_id)
-        t_h = torch.empty((4, b, n0, coef[1], coef[2]), dtype=x.dtype, device=x.device)
-        for wb in range(2):
-            axis_fwd(_outer_axis_inner(t_w[wb], 2), n1, b * n0, coef[2], _outer_axis_inner(t_h[wb], 2), _outer_axis_inner(t_h[2 + wb], 2),
-                     mode_id)
-        for pl in range(4):
-            axis_fwd(_outer_axis_inner(t_h[pl], 1), n0, b, coef[1] * coef[2], buf[:, pl].reshape(b, coef[0], -1),
-                     buf[:, 4 + pl].reshape(b, coef[0], -1), mode_id)
-    else:
-        raise NotImplementedError("boundary-wavelet levels exist for one, two and three transformed axes")
+    # One pass per axis, last axis first: 1 (+ 2 (+ 4)) launches.  Stage k holds 2^k planes; the pass over plane p writes its low band
+    # to plane p and its high band to plane p + 2^k; the planes of the last stage are the bands of `buf`.
+    cur = [x]
+    for axis in range(ndim, 0, -1):
+        npl = len(cur)
+        if axis == 1:
+            out = [buf[:, s] for s in range(2 * npl)]
+        else:
+            out = torch.empty((2 * npl, b, *sig[:axis - 1], *coef[axis - 1:]), dtype=x.dtype, device=x.device)
+        n, outer, inner = sig[axis - 1], b * int(np.prod(sig[:axis - 1])), int(np.prod(coef[axis:]))
+        for pl in range(npl):
+            src, o_lo, o_hi = (_outer_axis_inner(t, axis) for t in (cur[pl], out[pl], out[npl + pl]))
+            _launch(0, KID_AXIS_FWD, (n,), src, lambda stream: lib.mifwt_bwt_axis_fwd(
+                dt, L, mode_id, outer, n, inner, src.data_ptr(), _axis_strides(src), o_lo.data_ptr(), _axis_strides(o_lo), o_hi.data_ptr(),
+                _axis_strides(o_hi), lo, hi, ctypes.byref(tab), stream))
+        cur = out
     return buf
 
 
@@ -283,64 +285,38 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
     bands = [_unit_last(t) for t in bands]
     if len({t.stride() for t in bands[1:]}) > 1:
         bands = [bands[0]] + [t.contiguous() for t in bands[1:]]
-    y = torch.empty((a0.shape[0], *sig), dtype=a0.dtype, device=a0.device)
+    b = a0.shape[0]
+    y = torch.empty((b, *sig), dtype=a0.dtype, device=a0.device)
     if y.numel() == 0:
         return y
     lib = _lib()
-    key = (1, a0.shape, tuple(sig), bands[0].stride(), bands[1].stride(), a0.dtype, L)
-    p = _plans.get(key)
-    if p is None:
-        d = _desc(ndim, a0.dtype, _ZERO, L, a0.shape[0], sig, y.stride(), coef, bands[0].stride(), bands[1].stride())
-        kid = (lib.mifwt_bwt3_kernel_id if ndim == 3 else lib.mifwt_bwt_kernel_id)(ctypes.byref(d), 1)
-        if kid < 0 and kid != -2:
-            _engine._check(kid)
-        p = _plans[key] = (d, ctypes.byref(d), kid, 0)
-    d, ref, kid, _ = p
-    if kid == KID_INV3 and _composed3(1, a0.dtype, L):
-        kid = -2
+    ref, kid = _route(1, (1, a0.shape, tuple(sig), bands[0].stride(), bands[1].stride(), a0.dtype, L), ndim, a0.dtype, L,
+                      lambda: _desc(ndim, a0.dtype, _ZERO, L, b, sig, y.stride(), coef, bands[0].stride(), bands[1].stride()))
     tab = bk.tables(a0.device)
+    # (the C entries take the filters in rec order and reverse them into row filters)
+    lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
     if kid in (KID_INV, KID_INV3):
-        # (the C entry takes the filters in rec order and reverses them into row filters)
-        lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
         ptrs = _engine._arr(ctypes.c_void_p, len(bands) - 1)(*[t.data_ptr() for t in bands[1:]])
         ap, yp = bands[0].data_ptr(), y.data_ptr()
         entry = lib.mifwt_bwt3_inv if kid == KID_INV3 else lib.mifwt_bwt_inv
         _launch(1, kid, sig, a0, lambda stream: entry(ref, ap, ptrs, yp, lo, hi, ctypes.byref(tab), stream))
         return y
-    if a0.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"Input dtype {a0.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
-    dt = _engine._DTYPE_IDS[a0.dtype]
-    lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
-
-    def axis_inv(c_lo, c_hi, n, outer, inner, out):
-        _launch(1, KID_AXIS_INV, (n,), c_lo, lambda stream: lib.mifwt_bwt_axis_inv(
-            dt, L, outer, n, inner, c_lo.data_ptr(), _axis_strides(c_lo), c_hi.data_ptr(), _axis_strides(c_hi), out.data_ptr(), _axis_strides(out),
-            lo, hi, ctypes.byref(tab), stream))
-
-    if ndim == 1:
-        axis_inv(bands[0].unsqueeze(-1), bands[1].unsqueeze(-1), sig[0], a0.shape[0], 1, y.unsqueeze(-1))
-    elif ndim == 2:
-        b = a0.shape[0]
-        tmp = torch.empty((2, b, sig[0], coef[1]), dtype=a0.dtype, device=a0.device)
-        axis_inv(bands[0], bands[2], sig[0], b, coef[1], tmp[0])
-        axis_inv(bands[1], bands[3], sig[0], b, coef[1], tmp[1])
-        axis_inv(tmp[0].reshape(b * sig[0], coef[1], 1), tmp[1].reshape(b * sig[0], coef[1], 1), sig[1], b * sig[0], 1,
-                 y.reshape(b * sig[0], sig[1], 1))
-    elif ndim == 3:
-        # depth, height, width: 4 + 2 + 1 launches
-        b = a0.shape[0]
+    dt = _composed_setup(a0, ndim)
+    if ndim == 3:
         bands = [t.contiguous() for t in bands]
-        t_d = torch.empty((4, b, sig[0], coef[1], coef[2]), dtype=a0.dtype, device=a0.device)
-        for pl in range(4):
-            axis_inv(_outer_axis_inner(bands[pl], 1), _outer_axis_inner(bands[4 + pl], 1), sig[0], b, coef[1] * coef[2],
-                     _outer_axis_inner(t_d[pl], 1))
-        t_h = torch.empty((2, b, sig[0], sig[1], coef[2]), dtype=a0.dtype, device=a0.device)
-        for wb in range(2):
-            axis_inv(_outer_axis_inner(t_d[wb], 2), _outer_axis_inner(t_d[2 + wb], 2), sig[1], b * sig[0], coef[2],
-                     _outer_axis_inner(t_h[wb], 2))
-        axis_inv(_outer_axis_inner(t_h[0], 3), _outer_axis_inner(t_h[1], 3), sig[2], b * sig[0] * sig[1], 1, _outer_axis_inner(y, 3))
-    else:
-        raise NotImplementedError("boundary-wavelet levels exist for one, two and three transformed axes")
+    # The mirror of the analysis passes, first axis first: (4 +) (2 +) 1 launches.  The pass that leaves 2^k planes takes the low band
+    # from plane p and the high band from plane p + 2^k; the last one writes `y`.
+    cur = bands
+    for axis in range(1, ndim + 1):
+        npl = len(cur) // 2
+        out = [y] if axis == ndim else torch.empty((npl, b, *sig[:axis], *coef[axis:]), dtype=a0.dtype, device=a0.device)
+        n, outer, inner = sig[axis - 1], b * int(np.prod(sig[:axis - 1])), int(np.prod(coef[axis:]))
+        for pl in range(npl):
+            c_lo, c_hi, dst = (_outer_axis_inner(t, axis) for t in (cur[pl], cur[npl + pl], out[pl]))
+            _launch(1, KID_AXIS_INV, (n,), c_lo, lambda stream: lib.mifwt_bwt_axis_inv(
+                dt, L, outer, n, inner, c_lo.data_ptr(), _axis_strides(c_lo), c_hi.data_ptr(), _axis_strides(c_hi), dst.data_ptr(),
+                _axis_strides(dst), lo, hi, ctypes.byref(tab), stream))
+        cur = out
     return y
 
 

@@ -3,7 +3,7 @@
 // Replaces, per level of ptwt.MatrixWavedec3 / MatrixWaverec3 (reference src/ptwt/matmul_transform_3.py): three batched sparse products
 // with the level operator of each axis and the transposes between them, i.e. three trips of the volume through memory.  Here a level is
 // ONE launch that reads the volume once and writes the eight bands once (synthesis: reads the eight bands, writes the volume).  The row
-// bank (two filters + boundary table, see mifwt_bwt.hip for the matrix it stands for) is the same for every axis and every level.
+// bank (two filters + boundary table, see mifwt_bwt_rows.h for the matrix it stands for) is the same for every axis and every level.
 //
 // ENVELOPE: float32 / float64, even L <= 8 (haar, db2, db3, db4, bior2.2, rbio2.4 ...), unit innermost stride, every axis with
 // 2 ceil(n / 2) >= 2 (L - 1).  Longer filters do not fit a brick with a useful interior into 80 KB of LDS (the window of a brick grows by
@@ -25,42 +25,22 @@
 // (synthesis stages eight windows with L/2 coefficients of halo on either side of every axis, so its bricks for L >= 6 are small and
 // occupy a CU alone: the host layer routes synthesis levels of 6 / 8 taps to the composed passes and keeps these instances for
 // measurement and tests; whether a (direction, dtype, L) cell is routed here is decided on the host, _bwt.COMPOSED3_CELLS.)
-#include "mifwt_common.h"
+#include "mifwt_bwt_rows.h"
 
 namespace mifwt {
 
 namespace {
 
-template <typename T>
-struct Bwt3Vec;
-template <>
-struct Bwt3Vec<float> {
-  static constexpr int E = 4;
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <>
-struct Bwt3Vec<double> {
-  static constexpr int E = 2;
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-
-constexpr int round_up3(int v, int m) { return (v + m - 1) / m * m; }
-
-template <int L>
-struct Rows3 {
-  static constexpr int NT = (L - 2 + 3) / 4, NB = L / 4, NR = NT + NB, NTAB = NR > 0 ? NR : 1;
-};
-
 // ---- brick geometry (compile time) -------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 struct Fwd3Tile {
-  static constexpr int E = Bwt3Vec<T>::E;
+  static constexpr int E = BwtVec<T>::E;
   static constexpr int TC = 8 * E;                             // coefficient columns per brick: 8 lanes x one 16-byte store
   static constexpr int TD = L <= 6 ? 4 : 3;                    // coefficient slices per brick
   static constexpr int TR = L <= 4 ? 8 : (L == 6 ? 6 : (E == 4 ? 4 : 3));  // coefficient rows per brick
-  static constexpr int PADI = round_up3(L / 2 - 1, E);         // staged columns left of sample 2 mc0: interior bricks
-  static constexpr int PADE = round_up3(L - 2, E);             // ... bricks at an end (a bottom row's window reaches back L - 1 samples)
-  static constexpr int WC = round_up3(PADE + 2 * TC + L / 2 - 1, E);
+  static constexpr int PADI = round_up(L / 2 - 1, E);         // staged columns left of sample 2 mc0: interior bricks
+  static constexpr int PADE = round_up(L - 2, E);             // ... bricks at an end (a bottom row's window reaches back L - 1 samples)
+  static constexpr int WC = round_up(PADE + 2 * TC + L / 2 - 1, E);
   static constexpr int WR = 2 * TR + (L - 2) + L / 2 - 1;
   static constexpr int WD = 2 * TD + (L - 2) + L / 2 - 1;
   static constexpr int NTL = 2 * (L / 2 + 1) * L;              // table entries kept in LDS (>= 2 (nt + nb + 1) L)
@@ -69,12 +49,12 @@ struct Fwd3Tile {
 
 template <typename T, int L>
 struct Inv3Tile {
-  static constexpr int E = Bwt3Vec<T>::E;
+  static constexpr int E = BwtVec<T>::E;
   static constexpr int TQC = 8 * E;                            // coefficient columns per brick (2 TQC output samples)
   static constexpr int TQD = L <= 2 ? 4 : 2;                   // coefficient slices per brick
   static constexpr int TQR = L <= 2 ? 8 : (L == 8 && E == 2 ? 2 : 4);  // coefficient rows per brick
   static constexpr int PM = L <= 2 ? 0 : L / 2;                // staged coefficients either side (haar has no overlap)
-  static constexpr int PMC = round_up3(PM, E);
+  static constexpr int PMC = round_up(PM, E);
   static constexpr int WCM = TQC + 2 * PMC;
   static constexpr int WRM = TQR + 2 * PM;
   static constexpr int WDM = TQD + 2 * PM;
@@ -97,111 +77,14 @@ struct Bwt3Args {
   T lo[L], hi[L];            // f_lo, f_hi
 };
 
-// Table -> LDS: rows 0 .. nt+nb-1 the boundary rows, row nt+nb the plain taps in window order (c[k] = f[L-1-k]).
-template <typename T, int L>
-__device__ __forceinline__ void load_table3(T* tl, const Bwt3Args<T, L>& a) {
-  constexpr int NR = Rows3<L>::NR;
-  for (int i = threadIdx.x; i < 2 * (NR + 1) * L; i += blockDim.x) {
-    const int band = i / ((NR + 1) * L), r = (i / L) % (NR + 1), k = i % L;
-    T v;
-    if (r < NR)
-      v = (T)a.tab[(band * Rows3<L>::NTAB + r) * L + k];
-    else
-      v = band ? a.hi[L - 1 - k] : a.lo[L - 1 - k];
-    tl[i] = v;
-  }
-}
-
-// One staged vector of a row: LDS <- samples g0 .. g0 + E - 1 of a row with `n` real samples (padded extent n_pad); outside: 0, the
-// virtual sample: row[src].  `row` == nullptr: zeros.
-template <typename T, int E>
-__device__ __forceinline__ void stage_vec3(T* dst, const T* __restrict__ row, int g0, int n, int n_pad, int src, bool vec_ok) {
-  typedef typename Bwt3Vec<T>::type V;
-  V v;
-  if (row && vec_ok && g0 >= 0 && g0 + E <= n) {
-    v = *reinterpret_cast<const V*>(row + g0);
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int g = g0 + e;
-      T s = T(0);
-      if (row && g >= 0 && g < n_pad) {
-        if (g < n)
-          s = row[g];
-        else if (src >= 0)
-          s = row[src];
-      }
-      v[e] = s;
-    }
-  }
-  *reinterpret_cast<V*>(dst) = v;
-}
-
-// E consecutive analysis outputs (both bands) along a staged row.  `pad` = staged samples left of sample 2 * (first coefficient of the brick).
-template <typename T, int L, bool EDGE>
-__device__ __forceinline__ void analysis_row3(const T* xr, int pad, int ml, int m_glob, int m_ext, const T* tl, const T (&flo)[L],
-                                              const T (&fhi)[L], typename Bwt3Vec<T>::type& lo, typename Bwt3Vec<T>::type& hi) {
-  constexpr int E = Bwt3Vec<T>::E, NT = Rows3<L>::NT, NB = Rows3<L>::NB, NR = NT + NB;
-  if (!EDGE) {
-    // the window starts OFF samples into a 16-byte aligned run of the staged row (2 ml, pad and PADI are multiples of E)
-    typedef typename Bwt3Vec<T>::type V;
-    constexpr int PADI = round_up3(L / 2 - 1, E), OFF = PADI - (L / 2 - 1), NV = (OFF + 2 * E + L - 2 + E - 1) / E;
-    T w[NV * E];
-    const T* p = xr + 2 * ml + pad - PADI;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const V v = *reinterpret_cast<const V*>(p + i * E);
-#pragma unroll
-      for (int e = 0; e < E; ++e) w[i * E + e] = v[e];
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      T sl = T(0), sh = T(0);
-#pragma unroll
-      for (int k = 0; k < L; ++k) {
-        sl = fma(flo[L - 1 - k], w[OFF + 2 * e + k], sl);
-        sh = fma(fhi[L - 1 - k], w[OFF + 2 * e + k], sh);
-      }
-      lo[e] = sl;
-      hi[e] = sh;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int m = m_glob + e;
-      int r = NR, w0 = 2 * (ml + e) + pad - (L / 2 - 1);
-      if (m < NT) {
-        r = m;
-        w0 = pad - 2 * (m_glob - ml);  // sample 0
-      } else if (m >= m_ext - NB) {
-        r = NT + m - (m_ext - NB);
-        w0 = 2 * m_ext - L - 2 * (m_glob - ml) + pad;  // sample N - L
-      }
-      T sl = T(0), sh = T(0);
-      if (m < m_ext) {
-        const T* cl = tl + r * L;
-        const T* ch = tl + (NR + 1 + r) * L;
-#pragma unroll
-        for (int k = 0; k < L; ++k) {
-          const T v = xr[w0 + k];
-          sl = fma(cl[k], v, sl);
-          sh = fma(ch[k], v, sh);
-        }
-      }
-      lo[e] = sl;
-      hi[e] = sh;
-    }
-  }
-}
-
 // One analysis output pair ACROSS rows / slices: coefficient m (brick-local index ml) of an axis whose window entries are `pitch` elements
 // apart in LDS, E columns at a time.  ws = first staged sample of the axis, pad = 2 * (first coefficient of the brick) - ws.
 template <typename T, int L>
 __device__ __forceinline__ void analysis_across3(const T* col, int pitch, bool edge, int ml, int m, int m_ext, int pad, int ws, const T* tl,
-                                                 const T (&flo)[L], const T (&fhi)[L], typename Bwt3Vec<T>::type& lo,
-                                                 typename Bwt3Vec<T>::type& hi) {
-  typedef typename Bwt3Vec<T>::type V;
-  constexpr int NT = Rows3<L>::NT, NB = Rows3<L>::NB, NR = NT + NB;
+                                                 const T (&flo)[L], const T (&fhi)[L], typename BwtVec<T>::type& lo,
+                                                 typename BwtVec<T>::type& hi) {
+  typedef typename BwtVec<T>::type V;
+  constexpr int NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   V sl = V(0), sh = V(0);
   if (!edge || (m >= NT && m < m_ext - NB)) {
     const int w0 = 2 * ml + pad - (L / 2 - 1);
@@ -233,27 +116,15 @@ __device__ __forceinline__ void analysis_across3(const T* col, int pitch, bool e
   hi = sh;
 }
 
-template <typename T>
-__device__ __forceinline__ void store_vec3(T* p, const typename Bwt3Vec<T>::type& v, int valid, bool vec_ok) {
-  constexpr int E = Bwt3Vec<T>::E;
-  if (vec_ok && valid >= E) {
-    *reinterpret_cast<typename Bwt3Vec<T>::type*>(p) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-      if (e < valid) p[e] = v[e];
-  }
-}
-
 extern __shared__ __attribute__((aligned(16))) unsigned char bwt3_lds[];
 
 // ---- analysis ----------------------------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
   typedef Fwd3Tile<T, L> G;
-  typedef typename Bwt3Vec<T>::type V;
+  typedef typename BwtVec<T>::type V;
   constexpr int E = G::E, TC = G::TC, TR = G::TR, TD = G::TD, WC = G::WC, WR = G::WR, WD = G::WD, CG = TC / E;
-  constexpr int NT = Rows3<L>::NT, NB = Rows3<L>::NB, NR = NT + NB;
+  constexpr int NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   static_assert(WC >= 2 * TC, "the width image of a row must fit into the row it replaces");
   static_assert(2 * TD + L / 2 - 1 >= L && 2 * TR + L / 2 - 1 >= L, "the window of the first brick must hold the L samples of a top row");
   static_assert(WR * WC >= TR * 4 * TC, "the (height, width) image of a slice must fit into the slice it replaces");
@@ -274,12 +145,12 @@ __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
   const int padc = edge_c ? G::PADE : G::PADI;
   const int padr = edge_r ? L - 2 : L / 2 - 1;
   const int padd = edge_d ? L - 2 : L / 2 - 1;
-  const int wc = round_up3(padc + 2 * TC + L / 2 - 1, E);  // staged columns (<= WC)
+  const int wc = round_up(padc + 2 * TC + L / 2 - 1, E);  // staged columns (<= WC)
   const int wr = padr + 2 * TR + L / 2 - 1;                // staged rows (<= WR)
   const int wd = padd + 2 * TD + L / 2 - 1;                // staged slices (<= WD)
   const int ws_c = 2 * mc0 - padc, ws_r = 2 * mr0 - padr, ws_d = 2 * md0 - padd;
   const T* __restrict__ x = static_cast<const T*>(a.in[0]) + (int64_t)b * a.sig_bs;
-  if (edge_c || edge_r || edge_d) load_table3<T, L>(tl, a);
+  if (edge_c || edge_r || edge_d) load_table<T, L>(tl, a);
   const int vpr = wc / E;
   for (int i = tid; i < wd * wr * vpr; i += 256) {
     const int cv = i % vpr, r = (i / vpr) % wr, d = i / (vpr * wr);
@@ -290,7 +161,7 @@ __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
       if (gr >= a.n_r) gr = a.src_r;
       if (gd >= 0 && gr >= 0) row = x + (int64_t)gd * a.sig_ds + (int64_t)gr * a.sig_rs;
     }
-    stage_vec3<T, E>(xs + (d * WR + r) * WC + cv * E, row, ws_c + cv * E, a.n_c, 2 * a.m_c, a.src_c, a.sig_vec);
+    stage_vec<T, E>(xs + (d * WR + r) * WC + cv * E, row, ws_c + cv * E, a.n_c, 2 * a.m_c, a.src_c, a.sig_vec);
   }
   __syncthreads();
   // along the width, in place: row [wc samples] -> [TC low | TC high]
@@ -305,9 +176,9 @@ __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
         const int cg = i % CG, r = (i / CG) % wr, d = i / (CG * wr);
         const T* xr = xs + (d * WR + r) * WC;
         if (edge_c && (mc0 + cg * E < NT || mc0 + cg * E + E > a.m_c - NB))  // (only the lanes whose outputs include a boundary row)
-          analysis_row3<T, L, true>(xr, padc, cg * E, mc0 + cg * E, a.m_c, tl, a.lo, a.hi, lo[it], hi[it]);
+          analysis_run<T, L, true>(xr, padc, cg * E, mc0 + cg * E, a.m_c, tl, a.lo, a.hi, lo[it], hi[it]);
         else
-          analysis_row3<T, L, false>(xr, padc, cg * E, mc0 + cg * E, a.m_c, tl, a.lo, a.hi, lo[it], hi[it]);
+          analysis_run<T, L, false>(xr, padc, cg * E, mc0 + cg * E, a.m_c, tl, a.lo, a.hi, lo[it], hi[it]);
       }
     }
     __syncthreads();
@@ -360,64 +231,18 @@ __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
     const int valid = a.m_c - mc;
     const int64_t oa = (int64_t)b * a.a_bs + (int64_t)md * a.a_ds + (int64_t)mr * a.a_rs + mc;
     const int64_t od = (int64_t)b * a.d_bs + (int64_t)md * a.d_ds + (int64_t)mr * a.d_rs + mc;
-    store_vec3<T>(static_cast<T*>(a.out[pl]) + (pl ? od : oa), lo, valid, a.coef_vec);
-    store_vec3<T>(static_cast<T*>(a.out[4 + pl]) + od, hi, valid, a.coef_vec);
+    store_vec<T>(static_cast<T*>(a.out[pl]) + (pl ? od : oa), lo, valid, a.coef_vec);
+    store_vec<T>(static_cast<T*>(a.out[4 + pl]) + od, hi, valid, a.coef_vec);
   }
 }
 
 // ---- synthesis ---------------------------------------------------------------------------------------------------------------------------
-// One synthesis output (sample n of an axis with M coefficients per band) from windows of the two bands.  get(band, i): window entry i
-// (scalar or vector), window entry 0 = coefficient m_org.
-template <int L>
-__device__ __forceinline__ bool synthesis_plain3(int n, int m_ext) {
-  const int p = (L / 2 - n) & 1, m0 = (n + p - L / 2) >> 1;
-  return m0 >= Rows3<L>::NT && m0 + L / 2 <= m_ext - Rows3<L>::NB && n >= L - 1 && n <= 2 * m_ext - L;
-}
-
-template <typename T, int L, bool EDGE, typename V, typename Get>
-__device__ __forceinline__ V synthesis_point3(int n, int m_org, int m_ext, const T* tl, const T (&flo)[L], const T (&fhi)[L], Get get) {
-  constexpr int NT = Rows3<L>::NT, NB = Rows3<L>::NB, NR = NT + NB;
-  const int p = (L / 2 - n) & 1;
-  const int m0 = (n + p - L / 2) >> 1;  // (even numerator: exact)
-  V acc = V(0);
-  if (!EDGE) {
-    if (p) {
-#pragma unroll
-      for (int k = 0; k < L / 2; ++k) acc += flo[2 * k + 1] * get(0, m0 - m_org + k) + fhi[2 * k + 1] * get(1, m0 - m_org + k);
-    } else {
-#pragma unroll
-      for (int k = 0; k < L / 2; ++k) acc += flo[2 * k] * get(0, m0 - m_org + k) + fhi[2 * k] * get(1, m0 - m_org + k);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < L / 2; ++k) {
-      const int m = m0 + k;
-      if (m >= NT && m < m_ext - NB) {
-        // (the plain taps in window order sit in table row NR: c[j] = f[L-1-j])
-        const T cl = tl[NR * L + (L - 1 - (p + 2 * k))], ch = tl[(NR + 1 + NR) * L + (L - 1 - (p + 2 * k))];
-        acc += cl * get(0, m - m_org) + ch * get(1, m - m_org);
-      }
-    }
-    if (n < L - 1) {
-      for (int m = 0; m < NT; ++m) acc += tl[m * L + n] * get(0, m - m_org) + tl[(NR + 1 + m) * L + n] * get(1, m - m_org);
-    }
-    const int jb = n - (2 * m_ext - L);
-    if (jb >= 1 && jb < L) {
-      for (int i = 0; i < NB; ++i) {
-        const int m = m_ext - NB + i;
-        acc += tl[(NT + i) * L + jb] * get(0, m - m_org) + tl[(NR + 1 + NT + i) * L + jb] * get(1, m - m_org);
-      }
-    }
-  }
-  return acc;
-}
-
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
   typedef Inv3Tile<T, L> G;
-  typedef typename Bwt3Vec<T>::type V;
+  typedef typename BwtVec<T>::type V;
   constexpr int E = G::E, TQC = G::TQC, TQR = G::TQR, TQD = G::TQD, WCM = G::WCM, WRM = G::WRM, WDM = G::WDM, CV = WCM / E;
-  constexpr int NR = Rows3<L>::NR;
+  constexpr int NR = Rows<L>::NR;
   T* const bs = reinterpret_cast<T*>(bwt3_lds);  // [8][WDM][WRM][WCM], then the images of the depth and the height pass
   T* const tl = bs + 8 * WDM * WRM * WCM;
   const int tid = threadIdx.x;
@@ -432,9 +257,9 @@ __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
   const bool edge_c = NR > 0 && (2 * qc0 < L + 2 || 2 * (qc0 + TQC) + L + 2 >= 2 * a.m_c);
   const bool edge_r = NR > 0 && (2 * qr0 < L + 2 || 2 * (qr0 + TQR) + L + 2 >= 2 * a.m_r);
   const bool edge_d = NR > 0 && (2 * qd0 < L + 2 || 2 * (qd0 + TQD) + L + 2 >= 2 * a.m_d);
-  // (a brick needs the table where one of its outputs is not a plain one: a superset of !synthesis_plain3 over its samples)
+  // (a brick needs the table where one of its outputs is not a plain one: a superset of !synthesis_plain over its samples)
   const int mo_c = qc0 - G::PMC, mo_r = qr0 - G::PM, mo_d = qd0 - G::PM;
-  if (edge_c || edge_r || edge_d) load_table3<T, L>(tl, a);
+  if (edge_c || edge_r || edge_d) load_table<T, L>(tl, a);
   // the windows of the eight bands
   for (int i = tid; i < 8 * WDM * WRM * CV; i += 256) {
     const int cv = i % CV, r = (i / CV) % WRM, d = (i / (CV * WRM)) % WDM, s = i / (CV * WRM * WDM);
@@ -443,7 +268,7 @@ __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
     if (md >= 0 && md < a.m_d && mr >= 0 && mr < a.m_r)
       row = static_cast<const T*>(a.in[s]) + (s ? (int64_t)b * a.d_bs + (int64_t)md * a.d_ds + (int64_t)mr * a.d_rs
                                                 : (int64_t)b * a.a_bs + (int64_t)md * a.a_ds + (int64_t)mr * a.a_rs);
-    stage_vec3<T, E>(bs + ((s * WDM + d) * WRM + r) * WCM + cv * E, row, mo_c + cv * E, a.m_c, a.m_c, -1, a.coef_vec);
+    stage_vec<T, E>(bs + ((s * WDM + d) * WRM + r) * WCM + cv * E, row, mo_c + cv * E, a.m_c, a.m_c, -1, a.coef_vec);
   }
   __syncthreads();
   // along the depth, in place: [8][WDM] -> [4 planes (bit 1 height, bit 0 width)][2 TQD output slices]
@@ -459,8 +284,8 @@ __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
         auto get = [&](int db, int idx) -> V { return *reinterpret_cast<const V*>(bs + (((db * 4 + pl) * WDM + idx) * WRM + r) * WCM + cv * E); };
         V o = V(0);
         if (n < 2 * a.m_d)
-          o = edge_d && !synthesis_plain3<L>(n, a.m_d) ? synthesis_point3<T, L, true, V>(n, mo_d, a.m_d, tl, a.lo, a.hi, get)
-                                                        : synthesis_point3<T, L, false, V>(n, mo_d, a.m_d, tl, a.lo, a.hi, get);
+          o = edge_d && !synthesis_plain<L>(n, a.m_d) ? synthesis_point<T, L, true, V>(n, mo_d, a.m_d, tl, a.lo, a.hi, get)
+                                                        : synthesis_point<T, L, false, V>(n, mo_d, a.m_d, tl, a.lo, a.hi, get);
         v[it] = o;
       }
     }
@@ -487,8 +312,8 @@ __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
         };
         V o = V(0);
         if (n < 2 * a.m_r)
-          o = edge_r && !synthesis_plain3<L>(n, a.m_r) ? synthesis_point3<T, L, true, V>(n, mo_r, a.m_r, tl, a.lo, a.hi, get)
-                                                        : synthesis_point3<T, L, false, V>(n, mo_r, a.m_r, tl, a.lo, a.hi, get);
+          o = edge_r && !synthesis_plain<L>(n, a.m_r) ? synthesis_point<T, L, true, V>(n, mo_r, a.m_r, tl, a.lo, a.hi, get)
+                                                        : synthesis_point<T, L, false, V>(n, mo_r, a.m_r, tl, a.lo, a.hi, get);
         v[it] = o;
       }
     }
@@ -512,16 +337,14 @@ __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
 #pragma unroll
     for (int e = 0; e < E; ++e)
       v[e] = (nc + e >= 2 * a.m_c) ? T(0)
-             : edge_c && !synthesis_plain3<L>(nc + e, a.m_c) ? synthesis_point3<T, L, true, T>(nc + e, mo_c, a.m_c, tl, a.lo, a.hi, get)
-                                                             : synthesis_point3<T, L, false, T>(nc + e, mo_c, a.m_c, tl, a.lo, a.hi, get);
-    store_vec3<T>(y + (int64_t)gd * a.sig_ds + (int64_t)gr * a.sig_rs + nc, v, a.n_c - nc, a.sig_vec);
+             : edge_c && !synthesis_plain<L>(nc + e, a.m_c) ? synthesis_point<T, L, true, T>(nc + e, mo_c, a.m_c, tl, a.lo, a.hi, get)
+                                                             : synthesis_point<T, L, false, T>(nc + e, mo_c, a.m_c, tl, a.lo, a.hi, get);
+    store_vec<T>(y + (int64_t)gd * a.sig_ds + (int64_t)gr * a.sig_rs + nc, v, a.n_c - nc, a.sig_vec);
   }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 constexpr int kMaxFused3 = 8;  // longest filter of the fused 3-D kernels
-
-bool aligned16_3(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // 0 = not served by the fused kernels, MIFWT_ERR_BADARG = inconsistent, 1 = served
 int fused3_check(const mifwt_level_desc* d) {
@@ -549,7 +372,7 @@ int fused3_check(const mifwt_level_desc* d) {
 template <typename T, int L>
 int launch_fused3(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* flo, const double* fhi,
                   const mifwt_bwt_tables* tb, hipStream_t stream) {
-  constexpr int E = Bwt3Vec<T>::E;
+  constexpr int E = BwtVec<T>::E;
   typedef Fwd3Tile<T, L> GF;
   typedef Inv3Tile<T, L> GI;
   static_assert(GF::LDS3 <= 80 * 1024, "analysis brick: two workgroups per CU");
@@ -574,9 +397,9 @@ int launch_fused3(const mifwt_level_desc* d, int inverse, const void* const* in,
   a.src_r = ext_index(a.n_r, a.n_r, d->mode);
   a.src_c = ext_index(a.n_c, a.n_c, d->mode);
   const void* sig = inverse ? (const void*)out[0] : in[0];
-  a.sig_vec = aligned16_3(sig) && a.sig_bs % E == 0 && a.sig_ds % E == 0 && a.sig_rs % E == 0;
+  a.sig_vec = aligned16(sig) && a.sig_bs % E == 0 && a.sig_ds % E == 0 && a.sig_rs % E == 0;
   a.coef_vec = a.a_bs % E == 0 && a.a_ds % E == 0 && a.a_rs % E == 0 && a.d_bs % E == 0 && a.d_ds % E == 0 && a.d_rs % E == 0;
-  for (int s = 0; s < 8; ++s) a.coef_vec = a.coef_vec && aligned16_3(inverse ? in[s] : (const void*)out[s]);
+  for (int s = 0; s < 8; ++s) a.coef_vec = a.coef_vec && aligned16(inverse ? in[s] : (const void*)out[s]);
   a.tab = tb->rows;
   for (int t = 0; t < L; ++t) {
     a.lo[t] = (T)flo[t];
@@ -623,16 +446,13 @@ int bwt3_level(const mifwt_level_desc* d, int inverse, const void* const* in, vo
   if (ok < 0) return ok;
   if (!lo || !hi || !tb || !tb->rows) return MIFWT_ERR_BADARG;
   const int L = d->filt_len;
-  if (tb->n_top != (L - 2 + 3) / 4 || tb->n_bot != L / 4) return MIFWT_ERR_BADARG;
+  if (!table_fits(tb, L)) return MIFWT_ERR_BADARG;
   for (int s = 0; s < 8; ++s)
     if (!(inverse ? in[s] : (const void*)out[s])) return MIFWT_ERR_BADARG;
   if (!(inverse ? (const void*)out[0] : in[0])) return MIFWT_ERR_BADARG;
   if (!ok) return MIFWT_ERR_UNSUPPORTED;
   double flo[MIFWT_MAX_FILT], fhi[MIFWT_MAX_FILT];
-  for (int t = 0; t < L; ++t) {  // synthesis: the rows of S^T are built from the reversed rec_* filters
-    flo[t] = inverse ? lo[L - 1 - t] : lo[t];
-    fhi[t] = inverse ? hi[L - 1 - t] : hi[t];
-  }
+  bank_taps(inverse, L, lo, hi, flo, fhi);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return d->dtype == MIFWT_F32 ? dispatch_len3<float>(d, inverse, in, out, flo, fhi, tb, st)
                                : dispatch_len3<double>(d, inverse, in, out, flo, fhi, tb, st);

@@ -10,7 +10,7 @@
 //     computes both children's sample m,  o = (2q + band) * (h/2) + m  — i.e. child c = o / (h/2), q = c >> 1, band = c & 1 —
 //       interior rows:   y = sum_t f_band[t] x[q h + 2m + L/2 - t]
 //       top rows    m <  nt = ceil((L-2)/4):   table row m        over samples q h + 0 .. L-1
-//       bottom rows m >= h/2 - nb, nb = L/4:   table row nt + ..  over samples q h + h-L .. h-1          (layout: DESIGN.md §4.12)
+//       bottom rows m >= h/2 - nb, nb = L/4:   table row nt + ..  over samples q h + h-L .. h-1          (layout: mifwt_bwt_rows.h)
 //   synthesis (id 33), output position o in [0, n): node q = o / h, sample i = o % h, bands at q h (+ h/2):
 //       y = sum_band sum_{k<L/2} g[p+2k] c[m0+k] (interior rows) + column i of the table rows,  p = (L/2-i)&1, m0 = (i+p-L/2)/2
 //     with the synthesis bank (reversed rec_* filters and ITS tables: S != A^T for biorthogonal banks).
@@ -19,7 +19,7 @@
 // with 16-byte stores while it is the input of the next level.  The table sits in LDS, converted like the taps; only lanes that own a
 // boundary row read it.  Envelope (host): f32 / f64, even L <= 20, every fused level's input node even and >= 2 (L-1), two images of
 // n samples <= 64 KB.
-#include "mifwt_common.h"
+#include "mifwt_bwt_rows.h"
 
 namespace mifwt {
 
@@ -27,25 +27,6 @@ namespace {
 
 constexpr int TREE_MAX_LEVELS = 16;
 constexpr int TREE_IMAGE_BYTES = 32768;  // one LDS image: n <= 8192 f32 / 4096 f64
-
-template <typename T>
-struct TreeVec;
-template <>
-struct TreeVec<float> {
-  static constexpr int E = 4;
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <>
-struct TreeVec<double> {
-  static constexpr int E = 2;
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-
-template <int L>
-struct TreeRows {
-  static constexpr int NT = (L - 2 + 3) / 4, NB = L / 4, NR = NT + NB, NTAB = NR > 0 ? NR : 1;
-  static constexpr int TL = 2 * (NR + 1) * L;  // LDS table entries: per band the boundary rows, then the plain taps in window order
-};
 
 template <typename T, int L>
 struct TreeArgs {
@@ -60,24 +41,10 @@ struct TreeArgs {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char bwt_tree_lds[];
 
-template <typename T, int L>
-__device__ __forceinline__ void tree_load_table(T* tl, const TreeArgs<T, L>& a) {
-  constexpr int NR = TreeRows<L>::NR;
-  for (int i = threadIdx.x; i < TreeRows<L>::TL; i += blockDim.x) {
-    const int band = i / ((NR + 1) * L), r = (i / L) % (NR + 1), k = i % L;
-    T v;
-    if (r < NR)
-      v = (T)a.tab[(band * TreeRows<L>::NTAB + r) * L + k];
-    else
-      v = band ? a.hi[L - 1 - k] : a.lo[L - 1 - k];
-    tl[i] = v;
-  }
-}
-
 template <typename T>
 __device__ __forceinline__ void tree_stage(T* img, const T* __restrict__ src, int n, bool vec) {
-  typedef typename TreeVec<T>::type V;
-  constexpr int E = TreeVec<T>::E;
+  typedef typename BwtVec<T>::type V;
+  constexpr int E = BwtVec<T>::E;
   if (vec) {
     for (int i = threadIdx.x; i < n / E; i += blockDim.x) reinterpret_cast<V*>(img)[i] = reinterpret_cast<const V*>(src)[i];
   } else {
@@ -87,8 +54,8 @@ __device__ __forceinline__ void tree_stage(T* img, const T* __restrict__ src, in
 
 template <typename T>
 __device__ __forceinline__ void tree_flush(T* __restrict__ dst, const T* img, int n, bool vec) {
-  typedef typename TreeVec<T>::type V;
-  constexpr int E = TreeVec<T>::E;
+  typedef typename BwtVec<T>::type V;
+  constexpr int E = BwtVec<T>::E;
   if (vec) {
     for (int i = threadIdx.x; i < n / E; i += blockDim.x) reinterpret_cast<V*>(dst)[i] = reinterpret_cast<const V*>(img)[i];
   } else {
@@ -99,13 +66,13 @@ __device__ __forceinline__ void tree_flush(T* __restrict__ dst, const T* img, in
 // ---- analysis ------------------------------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_tree_fwd_kernel(const TreeArgs<T, L> a) {
-  constexpr int NT = TreeRows<L>::NT, NB = TreeRows<L>::NB, NR = TreeRows<L>::NR;
+  constexpr int NT = Rows<L>::NT, NB = Rows<L>::NB, NR = Rows<L>::NR;
   const int n = a.n;
   T* cur = reinterpret_cast<T*>(bwt_tree_lds);
   T* nxt = cur + n;
   T* tl = cur + 2 * n;
   const int64_t row = blockIdx.x;
-  tree_load_table<T, L>(tl, a);
+  load_table<T, L>(tl, a);
   tree_stage<T>(cur, a.in + row * a.in_rs, n, a.in_vec);
   __syncthreads();
   for (int lev = 0; lev < a.nlev; ++lev) {
@@ -149,13 +116,13 @@ __global__ void __launch_bounds__(256) bwt_tree_fwd_kernel(const TreeArgs<T, L> 
 // ---- synthesis -----------------------------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_tree_inv_kernel(const TreeArgs<T, L> a) {
-  constexpr int NT = TreeRows<L>::NT, NB = TreeRows<L>::NB, NR = TreeRows<L>::NR;
+  constexpr int NT = Rows<L>::NT, NB = Rows<L>::NB, NR = Rows<L>::NR;
   const int n = a.n;
   T* cur = reinterpret_cast<T*>(bwt_tree_lds);
   T* nxt = cur + n;
   T* tl = cur + 2 * n;
   const int64_t row = blockIdx.x;
-  tree_load_table<T, L>(tl, a);
+  load_table<T, L>(tl, a);
   tree_stage<T>(cur, a.in + row * a.in_rs, n, a.in_vec);
   __syncthreads();
   for (int lev = a.nlev - 1; lev >= 0; --lev) {
@@ -207,8 +174,6 @@ __global__ void __launch_bounds__(256) bwt_tree_inv_kernel(const TreeArgs<T, L> 
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
-bool tree_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int tree_elem_bytes(int dtype) { return dtype == MIFWT_F32 ? 4 : dtype == MIFWT_F64 ? 8 : 0; }
 
 // number of consecutive levels one launch takes from a node of n samples (0: none)
@@ -227,17 +192,17 @@ int tree_levels(int dtype, int filt_len, int64_t n, int max_levels) {
 template <typename T, int L>
 int tree_launch(int inverse, int64_t rows, int n, int64_t in_rs, int nlevels, const void* in, void* const* levels, const double* flo,
                 const double* fhi, const mifwt_bwt_tables* tb, hipStream_t stream) {
-  constexpr int E = TreeVec<T>::E;
+  constexpr int E = BwtVec<T>::E;
   TreeArgs<T, L> a;
   a.in = static_cast<const T*>(in);
   a.in_rs = in_rs;
   a.n = n;
   a.nlev = nlevels;
-  a.in_vec = tree_aligned16(in) && in_rs % E == 0 && n % E == 0;
+  a.in_vec = aligned16(in) && in_rs % E == 0 && n % E == 0;
   a.out_vec = n % E == 0;
   for (int i = 0; i < TREE_MAX_LEVELS; ++i) {
     a.lev[i] = i < nlevels ? static_cast<T*>(levels[i]) : nullptr;
-    if (i < nlevels) a.out_vec = a.out_vec && tree_aligned16(levels[i]);
+    if (i < nlevels) a.out_vec = a.out_vec && aligned16(levels[i]);
   }
   a.tab = tb->rows;
   for (int t = 0; t < L; ++t) {
@@ -245,16 +210,16 @@ int tree_launch(int inverse, int64_t rows, int n, int64_t in_rs, int nlevels, co
     a.hi[t] = (T)fhi[t];
   }
   if (rows == 0) return MIFWT_OK;
-  const int lds = (2 * n + TreeRows<L>::TL) * (int)sizeof(T);
+  const int lds = (2 * n + Rows<L>::TL) * (int)sizeof(T);
   const dim3 g((unsigned)rows), blk(256);
   if (inverse) {
     static DynLdsOnce once;
-    if (lds > 65536 && !once.ensure(reinterpret_cast<const void*>(&bwt_tree_inv_kernel<T, L>), 2 * TREE_IMAGE_BYTES + TreeRows<L>::TL * (int)sizeof(T)))
+    if (lds > 65536 && !once.ensure(reinterpret_cast<const void*>(&bwt_tree_inv_kernel<T, L>), 2 * TREE_IMAGE_BYTES + Rows<L>::TL * (int)sizeof(T)))
       return MIFWT_ERR_LAUNCH;
     hipLaunchKernelGGL((bwt_tree_inv_kernel<T, L>), g, blk, lds, stream, a);
   } else {
     static DynLdsOnce once;
-    if (lds > 65536 && !once.ensure(reinterpret_cast<const void*>(&bwt_tree_fwd_kernel<T, L>), 2 * TREE_IMAGE_BYTES + TreeRows<L>::TL * (int)sizeof(T)))
+    if (lds > 65536 && !once.ensure(reinterpret_cast<const void*>(&bwt_tree_fwd_kernel<T, L>), 2 * TREE_IMAGE_BYTES + Rows<L>::TL * (int)sizeof(T)))
       return MIFWT_ERR_LAUNCH;
     hipLaunchKernelGGL((bwt_tree_fwd_kernel<T, L>), g, blk, lds, stream, a);
   }
@@ -289,14 +254,11 @@ int tree_call(int inverse, int dtype, int filt_len, int64_t rows, int64_t n, int
   if (!in || !levels || !lo || !hi || !tb || !tb->rows) return MIFWT_ERR_BADARG;
   if (nlevels < 2 || (filt_len & 1) || filt_len > 20 || tree_levels(dtype, filt_len, n, nlevels) != nlevels) return MIFWT_ERR_UNSUPPORTED;
   if (rows > INT32_MAX || (inverse ? in_rs != n : in_rs < n)) return MIFWT_ERR_UNSUPPORTED;
-  if (tb->n_top != (filt_len - 2 + 3) / 4 || tb->n_bot != filt_len / 4) return MIFWT_ERR_BADARG;
+  if (!table_fits(tb, filt_len)) return MIFWT_ERR_BADARG;
   for (int i = 0; i < nlevels; ++i)
     if (!levels[i]) return MIFWT_ERR_BADARG;
   double flo[MIFWT_MAX_FILT], fhi[MIFWT_MAX_FILT];
-  for (int t = 0; t < filt_len; ++t) {  // synthesis: the rows of S^T are built from the reversed rec_* filters
-    flo[t] = inverse ? lo[filt_len - 1 - t] : lo[t];
-    fhi[t] = inverse ? hi[filt_len - 1 - t] : hi[t];
-  }
+  bank_taps(inverse, filt_len, lo, hi, flo, fhi);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return dtype == MIFWT_F32 ? tree_dispatch<float>(filt_len, inverse, rows, (int)n, in_rs, nlevels, in, levels, flo, fhi, tb, st)
                             : tree_dispatch<double>(filt_len, inverse, rows, (int)n, in_rs, nlevels, in, levels, flo, fhi, tb, st);

@@ -64,11 +64,46 @@ def _bank_taps(wavelet, orthogonalization):
     return taps
 
 
-def _too_deep_warning(level, what, shape, curr_level, current, filt_len) -> None:
-    sys.stderr.write(
-        f"Warning: The selected number of decomposition levels {level} is too large for the given input {what} {shape}. At level "
-        f"{curr_level}, the current signal {current} is smaller than the filter length {filt_len}. Therefore, the transformation is "
-        f"only computed up to the decomposition level {curr_level - 1}.\n")
+def _plan_levels(level: int, shape: Sequence[int], filt_len: int):
+    """The level loop of the six classes (the reference's _construct_analysis_matrices / _construct_synthesis_matrices without the
+    matrices) for a shape of one, two or three extents -> (the even sizes per level and the coarsest approximation's, the pad flags
+    per level in axis order, whether anything was padded).  Writes the reference's warning where ``level`` is too deep."""
+    shape = tuple(shape)
+    size_list, pad_list, cur = [], [], shape
+    for curr_level in range(1, level + 1):
+        if min(cur) < filt_len:
+            given, current = {1: (f"size {shape[0]}", f"length {cur[0]}"), 2: (f"shape {shape}", f"height and width {cur}"),
+                              3: (f"shape {shape}", f"depth, height and width {cur}")}[len(shape)]
+            sys.stderr.write(
+                f"Warning: The selected number of decomposition levels {level} is too large for the given input {given}. At level "
+                f"{curr_level}, the current signal {current} is smaller than the filter length {filt_len}. Therefore, the "
+                f"transformation is only computed up to the decomposition level {curr_level - 1}.\n")
+            break
+        pad_list.append(tuple(n % 2 != 0 for n in cur))
+        cur = tuple(n + n % 2 for n in cur)
+        size_list.append(cur)
+        cur = tuple(n // 2 for n in cur)
+    size_list.append(cur)
+    return size_list, pad_list, any(any(pad) for pad in pad_list)
+
+
+def _synthesis_extents(approx_shape, levels, message: str):
+    """Shapes first (the reference's checks inside its level loop), then the device: ``levels`` holds the folded detail bands
+    [B, M..] per level, coarsest first.  The bands of a level must have the shape of the current approximation (``message``); a level
+    gives 2 M samples per axis, or the next level's extent where that is 2 M - 1.  -> the output extents per level."""
+    out_extents, cur = [], tuple(approx_shape)
+    for c_pos, bands in enumerate(levels):
+        if any(tuple(t.shape) != cur for t in bands):
+            raise ValueError(message)
+        pred = [2 * m for m in cur[1:]]
+        if c_pos < len(levels) - 1:
+            for a, nxt in enumerate(levels[c_pos + 1][0].shape[1:]):
+                if nxt != pred[a]:
+                    assert nxt == pred[a] - 1, "padding error, please open an issue on github"
+                    pred[a] = int(nxt)
+        out_extents.append(tuple(pred))
+        cur = (cur[0], *pred)
+    return out_extents
 
 
 def _mode_for(extents_per_level, mode) -> int:
@@ -104,26 +139,6 @@ class MatrixWavedec:
         self._bank = _bwt.bank(self._taps, orthogonalization, "analysis")
         self._op_meta = None
 
-    def _plan_levels(self) -> None:
-        """The reference's _construct_analysis_matrices (matmul_transform.py:310-354) without the matrices."""
-        self.size_list, self.pad_list, self.padded = [], [], False
-        filt_len = self._bank.filt_len
-        curr_length = self.input_length
-        for curr_level in range(1, self.level + 1):
-            if curr_length < filt_len:
-                _too_deep_warning(self.level, "size", self.input_length, curr_level, f"length {curr_length}", filt_len)
-                break
-            if curr_length % 2 != 0:
-                curr_length += 1
-                self.padded = True
-                self.pad_list.append(True)
-            else:
-                self.pad_list.append(False)
-            self.size_list.append(curr_length)
-            curr_length = curr_length // 2
-        self.size_list.append(curr_length)
-        self._built = True
-
     @property
     def sparse_fwt_operator(self) -> torch.Tensor:
         """The whole padding-free transform as one sparse matrix: ``torch.sparse.mm(op, data.T)`` is a batched FWT
@@ -156,7 +171,8 @@ class MatrixWavedec:
         elif self.level <= 0:
             raise ValueError("level must be a positive integer.")
         if not self._built or len(self.size_list) < 2 or re_build:
-            self._plan_levels()
+            sizes, pads, self.padded = _plan_levels(self.level, (self.input_length,), self._bank.filt_len)
+            self.size_list, self.pad_list, self._built = [s[0] for s in sizes], [p[0] for p in pads], True
         nlevels = len(self.size_list) - 1
         extents = [(n,)] + [(s // 2,) for s in self.size_list[: max(nlevels - 1, 0)]]
         mode_id = _mode_for(extents[:nlevels] if nlevels else [(n,)], self.odd_coeff_padding_mode)
@@ -192,22 +208,6 @@ class MatrixWaverec:
         self._bank = _bwt.bank(self._taps, orthogonalization, "synthesis")
         self._op_meta = None
 
-    def _plan_levels(self) -> None:
-        """The reference's _construct_synthesis_matrices (matmul_transform.py:603-642) without the matrices."""
-        self.size_list, self.padded = [], False
-        filt_len = self._bank.filt_len
-        curr_length = self.input_length
-        for curr_level in range(1, self.level + 1):
-            if curr_length < filt_len:
-                _too_deep_warning(self.level, "size", self.input_length, curr_level, f"length {curr_length}", filt_len)
-                break
-            if curr_length % 2 != 0:
-                curr_length += 1
-                self.padded = True
-            self.size_list.append(curr_length)
-            curr_length = curr_length // 2
-        self._built = True
-
     @property
     def sparse_ifwt_operator(self) -> torch.Tensor:
         """The whole padding-free inverse as one sparse matrix (reference matmul_transform.py:559-601)."""
@@ -238,26 +238,14 @@ class MatrixWaverec:
         input_length = int(folded[-1].shape[-1]) * 2
         if self.level != level or self.input_length != input_length or not self._built:
             self.level, self.input_length = level, input_length
-            self._plan_levels()
-        # shapes first (the reference's checks inside its level loop), then the device
-        out_lens = []
-        cur = tuple(folded[0].shape)
-        for c_pos, hi in enumerate(folded[1:]):
-            if cur != tuple(hi.shape):
-                raise ValueError("coefficients must have the same shape")
-            pred = 2 * cur[-1]
-            if c_pos < len(folded) - 2:
-                nxt = int(folded[c_pos + 2].shape[-1])
-                if nxt != pred:
-                    assert nxt == pred - 1, "padding error, please open an issue on github"
-                    pred = nxt
-            out_lens.append(pred)
-            cur = (cur[0], pred)
+            sizes, _, self.padded = _plan_levels(level, (input_length,), self._bank.filt_len)
+            self.size_list, self._built = [s[0] for s in sizes[:-1]], True  # (no entry for the coarsest approximation here)
+        out_extents = _synthesis_extents(folded[0].shape, [[hi] for hi in folded[1:]], "coefficients must have the same shape")
         _engine._require_gpu(folded[0])
         self._op_meta = (folded[0].device, folded[0].dtype)
         lo = folded[0]
-        for hi, n_out in zip(folded[1:], out_lens):
-            lo = _bwt.transposed([lo, hi], self._bank, (n_out,))
+        for hi, ext in zip(folded[1:], out_extents):
+            lo = _bwt.transposed([lo, hi], self._bank, ext)
         return layout.unfold(lo)
 
 

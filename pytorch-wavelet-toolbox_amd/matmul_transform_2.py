@@ -20,19 +20,13 @@ import torch
 from . import _bwt, _engine, _fwt
 from ._wavelets import as_wavelet
 from .constants import Wavelet, WaveletCoeff2d, WaveletDetailTuple2d
-from .matmul_transform import _bank_taps, _deprecated_alias, _mode_for, _too_deep_warning
+from .matmul_transform import _bank_taps, _deprecated_alias, _mode_for, _plan_levels, _synthesis_extents
 
 __all__ = ["MatrixWavedec2", "MatrixWaverec2"]
 
 _NON_SEPARABLE = ("separable=False is not implemented: the non-separable boundary transform orthogonalises the boundary rows of a 2-D "
                   "Kronecker matrix and yields different coefficients than the separable one; only the separable form (the default) "
                   "is built on this engine.")
-
-
-def _matrix_pad_2(height: int, width: int) -> Tuple[int, int, Tuple[bool, bool]]:
-    """src/ptwt/matmul_transform_2.py:234-242 — the tuple is (width padded, height padded)."""
-    pad = (width % 2 != 0, height % 2 != 0)
-    return height + height % 2, width + width % 2, pad
 
 
 class MatrixWavedec2:
@@ -65,24 +59,6 @@ class MatrixWavedec2:
         """Separable transforms have no single operator matrix (reference matmul_transform_2.py:352-383)."""
         raise NotImplementedError
 
-    def _plan_levels(self) -> None:
-        """The reference's _construct_analysis_matrices (matmul_transform_2.py:385-449) without the matrices."""
-        self.size_list, self.pad_list, self.padded = [], [], False
-        filt_len = self._bank.filt_len
-        h, w = self.input_signal_shape
-        for curr_level in range(1, self.level + 1):
-            if h < filt_len or w < filt_len:
-                _too_deep_warning(self.level, "shape", self.input_signal_shape, curr_level, f"height and width ({h}, {w})", filt_len)
-                break
-            h, w, pad = _matrix_pad_2(h, w)
-            if any(pad):
-                self.padded = True
-            self.pad_list.append(pad)
-            self.size_list.append((h, w))
-            h, w = h // 2, w // 2
-        self.size_list.append((h, w))
-        self._built = True
-
     def __call__(self, input_signal: torch.Tensor) -> WaveletCoeff2d:
         layout = _fwt._Layout(input_signal, 2, self.axes)
         x = layout.fold(input_signal)
@@ -98,7 +74,9 @@ class MatrixWavedec2:
         elif self.level <= 0:
             raise ValueError("level must be a positive integer.")
         if not self._built or len(self.size_list) < 2 or re_build:
-            self._plan_levels()
+            self.size_list, pads, self.padded = _plan_levels(self.level, self.input_signal_shape, self._bank.filt_len)
+            # (as in the reference, src/ptwt/matmul_transform_2.py:234-242, a pad tuple is (width padded, height padded))
+            self.pad_list, self._built = [p[::-1] for p in pads], True
         nlevels = len(self.size_list) - 1
         extents = [(height, width)] + [(s[0] // 2, s[1] // 2) for s in self.size_list[: max(nlevels - 1, 0)]]
         mode_id = _mode_for(extents[:nlevels], self.odd_coeff_padding_mode)
@@ -138,20 +116,6 @@ class MatrixWaverec2:
         """Separable transforms have no single operator matrix (reference matmul_transform_2.py:639-675)."""
         raise NotImplementedError
 
-    def _plan_levels(self) -> None:
-        """The reference's _construct_synthesis_matrices (matmul_transform_2.py:677-735): the warning and ``padded``."""
-        self.padded = False
-        filt_len = self._bank.filt_len
-        h, w = self.input_signal_shape
-        for curr_level in range(1, self.level + 1):
-            if h < filt_len or w < filt_len:
-                _too_deep_warning(self.level, "shape", self.input_signal_shape, curr_level, f"height and width ({h}, {w})", filt_len)
-                break
-            h, w, pad = _matrix_pad_2(h, w)
-            if any(pad):
-                self.padded = True
-            h, w = h // 2, w // 2
-
     def __call__(self, coefficients: WaveletCoeff2d) -> torch.Tensor:
         coefficients = tuple(coefficients)
         if not coefficients or not isinstance(coefficients[0], torch.Tensor):
@@ -174,23 +138,8 @@ class MatrixWaverec2:
             height, width = (int(s) * 2 for s in levels[-1][0].shape[-2:])
             if self.input_signal_shape != (height, width) or self.level != level:
                 self.input_signal_shape, self.level = (height, width), level
-                self._plan_levels()
-        # shapes first (the reference's checks inside its level loop), then the device
-        out_extents = []
-        cur = tuple(ll.shape)
-        for c_pos, bands in enumerate(levels):
-            for t in bands:
-                if tuple(t.shape) != cur:
-                    raise ValueError("All coefficients on each level must have the same shape")
-            pred = [2 * cur[-2], 2 * cur[-1]]
-            if c_pos < level - 1:
-                nxt = [int(s) for s in levels[c_pos + 1][0].shape[-2:]]
-                for a in range(2):
-                    if nxt[a] != pred[a]:
-                        assert nxt[a] == pred[a] - 1, "padding error, please open an issue on github"
-                        pred[a] = nxt[a]
-            out_extents.append(tuple(pred))
-            cur = (cur[0], *pred)
+                _, _, self.padded = _plan_levels(level, (height, width), self._bank.filt_len)  # (the warning and ``padded``)
+        out_extents = _synthesis_extents(ll.shape, levels, "All coefficients on each level must have the same shape")
         _engine._require_gpu(ll)
         for bands, ext in zip(levels, out_extents):
             lh, hl, hh = bands

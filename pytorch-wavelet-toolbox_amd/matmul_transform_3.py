@@ -20,35 +20,11 @@ import torch
 from . import _bwt, _engine, _fwt
 from ._wavelets import as_wavelet
 from .constants import Wavelet, WaveletCoeffNd
-from .matmul_transform import _bank_taps, _deprecated_alias, _mode_for, _too_deep_warning
+from .matmul_transform import _bank_taps, _deprecated_alias, _mode_for, _plan_levels, _synthesis_extents
 
 __all__ = ["MatrixWavedec3", "MatrixWaverec3"]
 
 _KEYS = _fwt._KEYS_ND[3]  # detail s (1 .. 7) has key _KEYS[s - 1]: bit 2 of s = depth, bit 1 = height, bit 0 = width high-pass
-
-
-def _matrix_pad_3(depth: int, height: int, width: int) -> Tuple[int, int, int, Tuple[bool, bool, bool]]:
-    """src/ptwt/matmul_transform_3.py:50-77 — the tuple is (depth padded, height padded, width padded)."""
-    pad = (depth % 2 != 0, height % 2 != 0, width % 2 != 0)
-    return depth + depth % 2, height + height % 2, width + width % 2, pad
-
-
-def _plan_levels_3(level: int, shape: Tuple[int, int, int], filt_len: int):
-    """The level loop both classes share: even sizes per level, pad tuples, whether anything was padded (the reference's
-    _construct_analysis_matrices / _construct_synthesis_matrices without the matrices)."""
-    size_list, pad_list, padded = [], [], False
-    d, h, w = shape
-    for curr_level in range(1, level + 1):
-        if d < filt_len or h < filt_len or w < filt_len:
-            _too_deep_warning(level, "shape", shape, curr_level, f"depth, height and width ({d}, {h}, {w})", filt_len)
-            break
-        d, h, w, pad = _matrix_pad_3(d, h, w)
-        padded = padded or any(pad)
-        pad_list.append(pad)
-        size_list.append((d, h, w))
-        d, h, w = d // 2, h // 2, w // 2
-    size_list.append((d, h, w))
-    return size_list, pad_list, padded
 
 
 class MatrixWavedec3:
@@ -89,7 +65,7 @@ class MatrixWavedec3:
         elif self.level <= 0:
             raise ValueError("level must be a positive integer.")
         if not self._built or len(self.size_list) < 2 or re_build:
-            self.size_list, self.pad_list, self.padded = _plan_levels_3(self.level, shape, self._bank.filt_len)
+            self.size_list, self.pad_list, self.padded = _plan_levels(self.level, shape, self._bank.filt_len)
             self._built = True
         nlevels = len(self.size_list) - 1
         extents = [shape] + [tuple(n // 2 for n in s) for s in self.size_list[: max(nlevels - 1, 0)]]
@@ -149,26 +125,8 @@ class MatrixWaverec3:
             shape = tuple(int(s) * 2 for s in levels[-1][-1].shape[-3:])
             if self.input_signal_shape != shape or self.level != level:
                 self.input_signal_shape, self.level = shape, level
-                _, _, self.padded = _plan_levels_3(level, shape, self._bank.filt_len)
-        # shapes first (the reference's checks inside its level loop), then the device
-        out_extents = []
-        cur = tuple(lll.shape)
-        for c_pos, bands in enumerate(levels):
-            first = tuple(bands[0].shape)
-            for t in bands:
-                if tuple(t.shape) != first:
-                    raise ValueError("All coefficients on each level must have the same shape")
-            if first != cur:
-                raise ValueError("All coefficients on each level must have the same shape")
-            pred = [2 * m for m in cur[-3:]]
-            if c_pos < level - 1:
-                nxt = [int(s) for s in levels[c_pos + 1][0].shape[-3:]]
-                for a in range(3):
-                    if nxt[a] != pred[a]:
-                        assert nxt[a] == pred[a] - 1, "padding error, please open an issue on github"
-                        pred[a] = nxt[a]
-            out_extents.append(tuple(pred))
-            cur = (cur[0], *pred)
+                _, _, self.padded = _plan_levels(level, shape, self._bank.filt_len)
+        out_extents = _synthesis_extents(lll.shape, levels, "All coefficients on each level must have the same shape")
         _engine._require_gpu(lll)
         for bands, ext in zip(levels, out_extents):
             lll = _bwt.transposed([lll] + bands, self._bank, ext)

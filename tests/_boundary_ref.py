@@ -1,6 +1,6 @@
 """The float64 CPU reference of the boundary-wavelet transforms for the tests: the level operators that
 ``ptwt_amd._boundary.level_coo`` / ``level_matrix`` build on the host (numpy, float64, never a kernel), applied with plain torch on
-the CPU — sparse for rows, dense for planes — and chained into multi-level transforms the way the reference's classes chain theirs
+the CPU along one, two or three axes — sparse for rows and volumes, dense for planes — and chained into multi-level transforms the way the reference's classes chain theirs
 (one virtual sample appended to an odd extent, dropped again between the levels of a synthesis).  Everything is differentiable torch.
 
 tests/test_boundary_host.py pins this chain to the reference library's goldens (ptwt_ref_boundary.npz, ptwt_ref_boundary_mid.npz);
@@ -64,37 +64,40 @@ def _apply(op, x, transpose=False):
     return out.reshape(*x.shape[:-1], out.shape[-1])
 
 
+def _along(op, x, dim, transpose=False):
+    return _apply(op, x.transpose(dim, -1), transpose=transpose).transpose(dim, -1)
+
+
 def rows_level(x, taps, which, mode, **kw):
-    """One analysis level: x [B, n0(, n1)] -> [B, 2^d, M0(, M1)], band s = 2 (row band) + (column band)."""
+    """One analysis level: x [B, n0(, n1(, n2))] -> [B, 2^d, M0(, M1(, M2))]; band plane s: bit (d-1-a) set = high-pass along axis a
+    (2-D: 2 (row band) + (column band); 3-D: the order of ``wavedec3``, "aad" = 1 ... "ddd" = 7).  Last axis first."""
     ndim = x.dim() - 1
     for a in range(ndim):
         x = with_virtual(x, 1 + a, mode)
-    dense = ndim == 2
-    c = _apply(rows_operator(taps, x.shape[-1], which, dense=dense, dtype=x.dtype, **kw), x)
-    if ndim == 1:
-        return c.reshape(x.shape[0], 2, -1)
-    c = _apply(rows_operator(taps, x.shape[-2], which, dense=dense, dtype=x.dtype, **kw), c.transpose(-1, -2)).transpose(-1, -2)
-    h, w = c.shape[1] // 2, c.shape[2] // 2
-    return c.reshape(x.shape[0], 2, h, 2, w).permute(0, 1, 3, 2, 4).reshape(x.shape[0], 4, h, w)
+    c = x
+    for dim in range(ndim, 0, -1):
+        c = _along(rows_operator(taps, c.shape[dim], which, dense=ndim == 2, dtype=x.dtype, **kw), c, dim)
+    half = [n // 2 for n in c.shape[1:]]
+    split = c.reshape(x.shape[0], *(v for m in half for v in (2, m)))
+    return split.permute(0, *range(1, 2 * ndim, 2), *range(2, 2 * ndim + 1, 2)).reshape(x.shape[0], 1 << ndim, *half)
 
 
 def transposed_level(bands, taps, which, out_extent, **kw):
-    """One synthesis level y = B^T c from the 2^d bands [B, M0(, M1)], cropped to ``out_extent`` (2 M or 2 M - 1 per axis)."""
+    """One synthesis level y = B^T c from the 2^d bands [B, M0(, M1(, M2))], cropped to ``out_extent`` (2 M or 2 M - 1 per axis)."""
     ndim = bands[0].dim() - 1
-    dense = ndim == 2
-    if ndim == 1:
-        c = torch.cat(list(bands), -1)
-        y = _apply(rows_operator(taps, c.shape[-1], which, dense=dense, dtype=c.dtype, **kw), c, transpose=True)
-        return y[:, : out_extent[0]]
-    c = torch.cat([torch.cat([bands[0], bands[1]], -1), torch.cat([bands[2], bands[3]], -1)], -2)
-    y = _apply(rows_operator(taps, c.shape[-1], which, dense=dense, dtype=c.dtype, **kw), c, transpose=True)
-    y = _apply(rows_operator(taps, c.shape[-2], which, dense=dense, dtype=c.dtype, **kw), y.transpose(-1, -2), transpose=True).transpose(-1, -2)
-    return y[:, : out_extent[0], : out_extent[1]]
+    y = list(bands)
+    for dim in range(-1, -ndim - 1, -1):
+        y = [torch.cat(y[i: i + 2], dim) for i in range(0, len(y), 2)]
+    y = y[0]
+    for dim in ((2, 1) if ndim == 2 else range(1, ndim + 1)):  # (planes: columns first, volumes: depth first — as they always were)
+        y = _along(rows_operator(taps, y.shape[dim], which, dense=ndim == 2, dtype=y.dtype, **kw), y, dim, transpose=True)
+    return y[(slice(None), *(slice(0, n) for n in out_extent))]
 
 
 def wavedec(x, taps, level, mode="zero", **kw):
-    """MatrixWavedec / MatrixWavedec2 on x [B, n] / [B, h, w]: the flat coefficient list [a, d_level, ..., d_1] (2-D: a, then lh, hl,
-    hh of each level, coarsest first).  A level whose input is shorter than the filter is not computed."""
+    """MatrixWavedec / MatrixWavedec2 / MatrixWavedec3 on x [B, n] / [B, h, w] / [B, d, h, w]: the flat coefficient list
+    [a, d_level, ..., d_1] (2-D: a, then lh, hl, hh of each level, coarsest first; 3-D: aaa, then the seven details of each level).
+    A level whose input is shorter than the filter along an axis is not computed."""
     ndim, L = x.dim() - 1, len(taps[0])
     lo, details = x, []
     for _ in range(level):
@@ -110,8 +113,8 @@ def wavedec(x, taps, level, mode="zero", **kw):
 
 
 def waverec(coeffs, taps, ndim, **kw):
-    """MatrixWaverec / MatrixWaverec2 on the flat list of :func:`wavedec`: the sample appended to an odd approximation is dropped
-    between levels but not after the last one."""
+    """MatrixWaverec / MatrixWaverec2 / MatrixWaverec3 on the flat list of :func:`wavedec`: the sample appended to an odd
+    approximation is dropped between levels but not after the last one."""
     per = (1 << ndim) - 1
     lo = coeffs[0]
     levels = [coeffs[1 + i: 1 + i + per] for i in range(0, len(coeffs) - 1, per)]

@@ -7,15 +7,24 @@ import torch
 from tests import _boundary_ref as R
 
 
-def tree_fwd(x, taps, k, **kw):
-    """x [R, n] -> the k level buffers [R, 2^i, n / 2^i], i = 1 .. k (analysis bank; every expanded node even)."""
-    rows, n = x.shape
-    out, cur = [], x.reshape(rows, 1, n)
-    for i in range(k):
+def packet_levels(x, taps, depth, **kw):
+    """Every level 1 .. depth of a full tree over x [R, n]: buffers [R, 2^i, m_i] (analysis bank; odd nodes get the zero virtual
+    sample)."""
+    rows = x.shape[0]
+    out, cur = [], x.reshape(rows, 1, -1)
+    for i in range(depth):
         flat = cur.reshape(-1, cur.shape[-1])
         cur = R.rows_level(flat, taps, "analysis", "zero", **kw).reshape(rows, 2 << i, -1)
         out.append(cur)
     return out
+
+
+tree_fwd = packet_levels  # x [R, n] -> the k level buffers [R, 2^i, n / 2^i], i = 1 .. k, where every expanded node is even
+
+
+def packet_leaves(x, taps, depth, **kw):
+    """Natural-order leaves [R, 2^depth, m] of a full tree over x [R, n]."""
+    return packet_levels(x, taps, depth, **kw)[-1] if depth else x.reshape(x.shape[0], 1, -1)
 
 
 def tree_inv(leaves, taps, k, **kw):
@@ -28,27 +37,6 @@ def tree_inv(leaves, taps, k, **kw):
         cur = y.reshape(rows, 1 << i, -1)
         out.append(cur)
     return out[::-1]
-
-
-def packet_leaves(x, taps, depth, **kw):
-    """Natural-order leaves [R, 2^depth, m] of a full tree over x [R, n] (odd nodes get the zero virtual sample)."""
-    rows = x.shape[0]
-    cur = x.reshape(rows, 1, -1)
-    for i in range(depth):
-        flat = cur.reshape(-1, cur.shape[-1])
-        cur = R.rows_level(flat, taps, "analysis", "zero", **kw).reshape(rows, 2 << i, -1)
-    return cur
-
-
-def packet_levels(x, taps, depth, **kw):
-    """Every level 1 .. depth of a full tree over x [R, n]: buffers [R, 2^i, m_i] (odd nodes get the zero virtual sample)."""
-    rows = x.shape[0]
-    out, cur = [], x.reshape(rows, 1, -1)
-    for i in range(depth):
-        flat = cur.reshape(-1, cur.shape[-1])
-        cur = R.rows_level(flat, taps, "analysis", "zero", **kw).reshape(rows, 2 << i, -1)
-        out.append(cur)
-    return out
 
 
 def packet_rec(leaves, taps, lengths, **kw):

@@ -339,7 +339,9 @@ def test_tile_table_of_the_gpu_tests_is_the_geometry_of_the_source():
                 nest -= 1
         raise AssertionError(e)
 
-    assert re.search(r"struct Bwt3Vec<float> \{\s*static constexpr int E = 4;", src) and re.search(r"struct Bwt3Vec<double> \{\s*static constexpr int E = 2;", src)
+    with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_bwt_rows.h")) as f:
+        rows = f.read()  # (the vector type is the row bank's, shared by the boundary-wavelet kernels)
+    assert re.search(r"struct BwtVec<float> \{\s*static constexpr int E = 4;", rows) and re.search(r"struct BwtVec<double> \{\s*static constexpr int E = 2;", rows)
     assert K.E == {torch.float32: 4, torch.float64: 2}
     assert K.FUSED == [2, 4, 6, 8] and all("MIFWT_BWT3_CASE(%d)" % flen in src for flen in K.FUSED) and "MIFWT_BWT3_CASE(10)" not in src
     assert "constexpr int kMaxFused3 = 8;" in src

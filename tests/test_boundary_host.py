@@ -359,7 +359,9 @@ def test_tile_table_of_the_gpu_kernel_tests_is_the_geometry_of_the_source():
         (expr,) = re.findall(r"static constexpr int %s = ([^;]+);" % name, src)
         return expr.strip()
 
-    assert re.search(r"struct BwtVec<float> \{\s*static constexpr int E = 4;", src) and re.search(r"struct BwtVec<double> \{\s*static constexpr int E = 2;", src)
+    with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_bwt_rows.h")) as f:
+        rows = f.read()  # (the vector type is the row bank's, shared by the boundary-wavelet kernels)
+    assert re.search(r"struct BwtVec<float> \{\s*static constexpr int E = 4;", rows) and re.search(r"struct BwtVec<double> \{\s*static constexpr int E = 2;", rows)
     assert K.E == {torch.float32: 4, torch.float64: 2}
     assert (const("TC1"), const("TC"), const("TR")) == ("256 * E", "16 * E", "8")
     assert (const("TQ1"), const("TQ"), const("TQC")) == ("128 * E", "16", "(L <= 12 ? 16 : 8) * E")

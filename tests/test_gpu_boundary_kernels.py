@@ -396,6 +396,48 @@ def test_a_few_hundred_rows_or_planes_per_kernel(kernel, dtype):
         _run_level(direction, dtype, random_bank(flen, 4), "synthesis", (2 * (tr + 3), 2 * (tc + 3) - 1), 200, "reflect", "contiguous")
 
 
+def test_composed_passes_launch_in_the_documented_order():
+    """The composed route is one loop over the axes: analysis runs the last axis first and doubles its planes per pass (1 + 2 + 4
+    launches of pass 28), synthesis mirrors it (4 + 2 + 1 of pass 29).  The recorded (kernel id, extent) lists are pinned, and the
+    values compared with the float64 operators."""
+    fwd, inv = _bwt.KID_AXIS_FWD, _bwt.KID_AXIS_INV
+    assert (fwd, inv) == (28, 29)
+    cases = [
+        (random_bank(22, 5), (50,), False, [(fwd, (50,))], [(inv, (50,))]),
+        (random_bank(22, 5), (44, 50), False, [(fwd, (50,))] + [(fwd, (44,))] * 2, [(inv, (44,))] * 2 + [(inv, (50,))]),
+        (random_bank(6, 5), (12, 14, 20), True, [(fwd, (20,))] + [(fwd, (14,))] * 2 + [(fwd, (12,))] * 4,
+         [(inv, (12,))] * 4 + [(inv, (14,))] * 2 + [(inv, (20,))]),
+    ]
+    gen = torch.Generator().manual_seed(2024)
+
+    def recorded(call):
+        _engine.level_events = []
+        try:
+            out = call()
+            events = [(e[1], e[2]) for e in _engine.level_events]
+        finally:
+            _engine.level_events = None
+        torch.cuda.synchronize()
+        return out, events
+
+    for taps, sig, force, want_fwd, want_inv in cases:
+        x = _rnd(gen, F32, 2, *sig)
+        bands = [_rnd(gen, F32, 2, *(n // 2 for n in sig)) for _ in range(1 << len(sig))]
+        keep = _bwt.FORCE_COMPOSED3
+        _bwt.FORCE_COMPOSED3 = force
+        try:
+            got, events = recorded(lambda: _bwt.rows_level(x, _bwt.bank(taps, "gramschmidt", "analysis"), _engine.MODE_IDS["zero"]))
+            assert events == want_fwd, (sig, events)
+            rec, events = recorded(lambda: _bwt.transposed_level(bands, _bwt.bank(taps, "gramschmidt", "synthesis"), sig))
+            assert events == want_inv, (sig, events)
+        finally:
+            _bwt.FORCE_COMPOSED3 = keep
+        want = BR.rows_level(x.double().cpu(), taps, "analysis", "zero")
+        for s in range(1 << len(sig)):
+            _check(got[:, s], want[:, s], LEVEL_TOL[F32], ("composed fwd", sig, "band", s))
+        _check(rec, BR.transposed_level([t.double().cpu() for t in bands], taps, "synthesis", sig), LEVEL_TOL[F32], ("composed inv", sig))
+
+
 def test_the_cell_lists_cover_what_they_claim():
     """(no GPU work) the 1-D counts sit on both sides of the synthesis kernels' edge condition 2 (qc0 + T) + L + 2 >= 2 M and include
     a last tile of boundary rows only; the planes put seams on each axis alone and on both, for both tile shapes."""
