@@ -15,7 +15,8 @@
 //      conflict-free), A = T from registers, f32 accumulate; result written TRANSPOSED as f16 ([band][column][row]) so
 //      that
 //   3. the vertical pass is the same GEMM with the same T: B = 16-byte column fragments, D -> global stores.
-// Taps enter the matrix cores as f16 PAIRS (t = t_hi + t_lo, two MFMAs per K-step): f32-accurate filters; the data are
+// Taps enter the matrix cores as f16 PAIRS (t = t_hi + t_lo, two MFMAs per K-step), built without scaling: accurate to 2^-24 ABSOLUTELY
+// (2^-25 for |t| < 1/2; the low half of a small tap is an f16 subnormal), not relatively — DESIGN.md 4.9; the data are
 // f16 by definition of this storage type, the intermediate (lo, hi) image is rounded to f16 once.
 // Envelope: f16 storage, even L in [18, 32] (shorter filters are HBM-bound in the vector kernels already).
 #include "mifwt_stream.h"

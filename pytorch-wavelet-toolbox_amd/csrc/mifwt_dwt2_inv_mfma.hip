@@ -9,7 +9,8 @@
 // output pairs is a banded product
 //     y[2 p0 .. 2 p0 + 32)  =  S (32 x 64) . [a[p0 .. p0 + 32); d[p0 .. p0 + 32)],     S[2q + r][32 b + q + i] = g_b[L-2-2i+r]
 // (zero elsewhere: half of S is structural zeros), i.e. the GEMM shape of the analysis kernel (mifwt_dwt2_fwd_mfma.hip): M = 32,
-// K = 64, N = rows / columns, v_mfma_f32_32x32x16_f16, four K-steps, taps as f16 pairs (t = t_hi + t_lo: f32-accurate filters).
+// K = 64, N = rows / columns, v_mfma_f32_32x32x16_f16, four K-steps, taps as f16 pairs (t = t_hi + t_lo: accurate to 2^-24
+// absolutely).
 //
 // The mirror of the analysis WALK: a workgroup walks down seg_tiles stacked tiles (32 output rows x 128 output columns) of one
 // column panel of an image.  Per tile the loader wave fetches the 16 NEW coefficient rows x 80 columns of the four bands (a "chunk":
