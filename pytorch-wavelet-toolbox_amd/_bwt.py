@@ -61,39 +61,20 @@ class BwtTables(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_void_p), ("n_top", ctypes.c_int32), ("n_bot", ctypes.c_int32)]
 
 
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = _engine.load_library()
-    if not _bound:
-        vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-        dbl_p, desc_p, tab_p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_engine.LevelDesc), ctypes.POINTER(BwtTables)
-        i64_p, vpp = ctypes.POINTER(i64), ctypes.POINTER(vp)
-        for name in ("mifwt_bwt_supported", "mifwt_bwt_kernel_id", "mifwt_bwt3_supported", "mifwt_bwt3_kernel_id"):
-            getattr(lib, name).restype = ci
-            getattr(lib, name).argtypes = [desc_p, ci]
-        lib.mifwt_bwt_fwd.restype = ci
-        lib.mifwt_bwt_fwd.argtypes = [desc_p, vp, vp, vpp, dbl_p, dbl_p, tab_p, vp]
-        lib.mifwt_bwt_inv.restype = ci
-        lib.mifwt_bwt_inv.argtypes = [desc_p, vp, vpp, vp, dbl_p, dbl_p, tab_p, vp]
-        for name in ("mifwt_bwt3_fwd", "mifwt_bwt3_inv"):
-            getattr(lib, name).restype = ci
-        lib.mifwt_bwt3_fwd.argtypes = lib.mifwt_bwt_fwd.argtypes
-        lib.mifwt_bwt3_inv.argtypes = lib.mifwt_bwt_inv.argtypes
-        lib.mifwt_bwt_axis_fwd.restype = ci
-        lib.mifwt_bwt_axis_fwd.argtypes = [ci, ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
-        lib.mifwt_bwt_axis_inv.restype = ci
-        lib.mifwt_bwt_axis_inv.argtypes = [ci, ci, i64, i64, i64, vp, i64_p, vp, i64_p, vp, i64_p, dbl_p, dbl_p, tab_p, vp]
-        lib.mifwt_bwt_tree_levels.restype = ci
-        lib.mifwt_bwt_tree_levels.argtypes = [ci, ci, i64, ci]
-        lib.mifwt_bwt_tree_fwd.restype = ci
-        lib.mifwt_bwt_tree_fwd.argtypes = [ci, ci, i64, i64, i64, ci, vp, vpp, dbl_p, dbl_p, tab_p, vp]
-        lib.mifwt_bwt_tree_inv.restype = ci
-        lib.mifwt_bwt_tree_inv.argtypes = [ci, ci, i64, i64, ci, vp, vpp, dbl_p, dbl_p, tab_p, vp]
-        _bound = True
-    return lib
+_ci, _i64, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+_dbl_p, _i64_p, _vpp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(_vp)
+_desc_p, _tab_p = ctypes.POINTER(_engine.LevelDesc), ctypes.POINTER(BwtTables)
+_FWD, _INV = [_desc_p, _vp, _vp, _vpp, _dbl_p, _dbl_p, _tab_p, _vp], [_desc_p, _vp, _vpp, _vp, _dbl_p, _dbl_p, _tab_p, _vp]
+_engine.register_entries({
+    **{name: (_ci, [_desc_p, _ci]) for name in ("mifwt_bwt_supported", "mifwt_bwt_kernel_id", "mifwt_bwt3_supported", "mifwt_bwt3_kernel_id")},
+    "mifwt_bwt_fwd": (_ci, _FWD), "mifwt_bwt_inv": (_ci, _INV), "mifwt_bwt3_fwd": (_ci, _FWD), "mifwt_bwt3_inv": (_ci, _INV),
+    "mifwt_bwt_axis_fwd": (_ci, [_ci, _ci, _ci, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _tab_p, _vp]),
+    "mifwt_bwt_axis_inv": (_ci, [_ci, _ci, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _tab_p, _vp]),
+    "mifwt_bwt_tree_levels": (_ci, [_ci, _ci, _i64, _ci]),
+    "mifwt_bwt_tree_fwd": (_ci, [_ci, _ci, _i64, _i64, _i64, _ci, _vp, _vpp, _dbl_p, _dbl_p, _tab_p, _vp]),
+    "mifwt_bwt_tree_inv": (_ci, [_ci, _ci, _i64, _i64, _ci, _vp, _vpp, _dbl_p, _dbl_p, _tab_p, _vp]),
+})
+_lib = _engine.load_library
 
 
 class Bank:
@@ -155,34 +136,11 @@ _plans: dict = {}
 _engine._routing_caches.append(_plans)
 
 
-def _desc(ndim, dtype, mode_id, flen, batch, sig, sig_stride, coef, a_stride, d_stride):
-    d = _engine.LevelDesc()
-    d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _engine._DTYPE_IDS[dtype], mode_id, flen, batch
-    for a in range(ndim):
-        d.sig_extent[a], d.coef_extent[a] = sig[a], coef[a]
-    for a in range(ndim + 1):
-        d.sig_stride[a], d.approx_stride[a], d.detail_stride[a] = sig_stride[a], a_stride[a], d_stride[a]
-    return d
+_desc, _unit_last = _engine._desc, _engine._unit_last
 
 
-def _launch(direction: int, kid: int, extent, anchor: torch.Tensor, call) -> None:
-    dev = anchor.device
-    with torch.cuda.device(dev):
-        if _engine.level_events is None:
-            rc = call(_engine._raw_stream(dev.index if dev.index is not None else torch.cuda.current_device()))
-        else:
-            stream = torch.cuda.current_stream(dev)
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record(stream)
-            rc = call(stream.cuda_stream)
-            ev[1].record(stream)
-            _engine.level_events.append((("bwt_fwd", "bwt_inv")[direction], kid, tuple(extent), ev[0], ev[1]))
-    if rc != 0:
-        _engine._check(rc)
-
-
-def _unit_last(t: torch.Tensor) -> torch.Tensor:
-    return t if t.stride(-1) == 1 or t.shape[-1] == 1 and t.is_contiguous() else t.contiguous()
+def _launch(direction: int, kid: int, extent, anchor: torch.Tensor, entry, *args) -> None:
+    _engine._run(("bwt_fwd", "bwt_inv")[direction], kid, extent, anchor, entry, args)
 
 
 def _axis_strides(t: torch.Tensor):
@@ -198,14 +156,14 @@ def _outer_axis_inner(t: torch.Tensor, axis: int) -> torch.Tensor:
 def _route(direction: int, key, ndim: int, dtype: torch.dtype, flen: int, desc):
     """(reference to the level descriptor, kernel id) of a level; -2: no fused kernel takes it, it runs the composed axis passes.
     The descriptor ``desc()`` builds and the kernel's answer are cached under ``key``."""
-    p = _plans.get(key)
-    if p is None:
+    def build():
         lib, d = _lib(), desc()
         kid = (lib.mifwt_bwt3_kernel_id if ndim == 3 else lib.mifwt_bwt_kernel_id)(ctypes.byref(d), direction)
         if kid < 0 and kid != -2:
             _engine._check(kid)
-        p = _plans[key] = (d, ctypes.byref(d), kid)
-    _, ref, kid = p
+        return d, ctypes.byref(d), kid
+
+    _, ref, kid = _engine._plan(key, build, _plans)
     if kid == (KID_FWD3, KID_INV3)[direction] and _composed3(direction, dtype, flen):
         kid = -2
     return ref, kid
@@ -247,8 +205,7 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
     if kid in (KID_FWD, KID_FWD3):
         base, xp = buf.data_ptr(), x.data_ptr()
         ptrs = _engine._band_ptrs(base, buf.stride(1) * x.element_size(), (1 << ndim) - 1)
-        entry = lib.mifwt_bwt3_fwd if kid == KID_FWD3 else lib.mifwt_bwt_fwd
-        _launch(0, kid, sig, x, lambda stream: entry(ref, xp, base, ptrs, lo, hi, ctypes.byref(tab), stream))
+        _launch(0, kid, sig, x, lib.mifwt_bwt3_fwd if kid == KID_FWD3 else lib.mifwt_bwt_fwd, ref, xp, base, ptrs, lo, hi, ctypes.byref(tab))
         return buf
     dt = _composed_setup(x, ndim)
     if ndim > 1:
@@ -265,9 +222,8 @@ def rows_level(x: torch.Tensor, bk: Bank, mode_id: int) -> torch.Tensor:
         n, outer, inner = sig[axis - 1], b * int(np.prod(sig[:axis - 1])), int(np.prod(coef[axis:]))
         for pl in range(npl):
             src, o_lo, o_hi = (_outer_axis_inner(t, axis) for t in (cur[pl], out[pl], out[npl + pl]))
-            _launch(0, KID_AXIS_FWD, (n,), src, lambda stream: lib.mifwt_bwt_axis_fwd(
-                dt, L, mode_id, outer, n, inner, src.data_ptr(), _axis_strides(src), o_lo.data_ptr(), _axis_strides(o_lo), o_hi.data_ptr(),
-                _axis_strides(o_hi), lo, hi, ctypes.byref(tab), stream))
+            _launch(0, KID_AXIS_FWD, (n,), src, lib.mifwt_bwt_axis_fwd, dt, L, mode_id, outer, n, inner, src.data_ptr(), _axis_strides(src),
+                    o_lo.data_ptr(), _axis_strides(o_lo), o_hi.data_ptr(), _axis_strides(o_hi), lo, hi, ctypes.byref(tab))
         cur = out
     return buf
 
@@ -283,8 +239,7 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
     if is_short(sig, L):
         return _transposed_dense(bands, bk, sig)
     bands = [_unit_last(t) for t in bands]
-    if len({t.stride() for t in bands[1:]}) > 1:
-        bands = [bands[0]] + [t.contiguous() for t in bands[1:]]
+    bands = [bands[0], *_engine._share_strides(bands[1:])[0]]
     b = a0.shape[0]
     y = torch.empty((b, *sig), dtype=a0.dtype, device=a0.device)
     if y.numel() == 0:
@@ -296,10 +251,8 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
     # (the C entries take the filters in rec order and reverse them into row filters)
     lo, hi = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi)
     if kid in (KID_INV, KID_INV3):
-        ptrs = _engine._arr(ctypes.c_void_p, len(bands) - 1)(*[t.data_ptr() for t in bands[1:]])
-        ap, yp = bands[0].data_ptr(), y.data_ptr()
-        entry = lib.mifwt_bwt3_inv if kid == KID_INV3 else lib.mifwt_bwt_inv
-        _launch(1, kid, sig, a0, lambda stream: entry(ref, ap, ptrs, yp, lo, hi, ctypes.byref(tab), stream))
+        _launch(1, kid, sig, a0, lib.mifwt_bwt3_inv if kid == KID_INV3 else lib.mifwt_bwt_inv, ref, bands[0].data_ptr(), _engine._ptr_array(bands[1:]),
+                y.data_ptr(), lo, hi, ctypes.byref(tab))
         return y
     dt = _composed_setup(a0, ndim)
     if ndim == 3:
@@ -313,9 +266,8 @@ def transposed_level(bands: Sequence[torch.Tensor], bk: Bank, out_extent: Sequen
         n, outer, inner = sig[axis - 1], b * int(np.prod(sig[:axis - 1])), int(np.prod(coef[axis:]))
         for pl in range(npl):
             c_lo, c_hi, dst = (_outer_axis_inner(t, axis) for t in (cur[pl], cur[npl + pl], out[pl]))
-            _launch(1, KID_AXIS_INV, (n,), c_lo, lambda stream: lib.mifwt_bwt_axis_inv(
-                dt, L, outer, n, inner, c_lo.data_ptr(), _axis_strides(c_lo), c_hi.data_ptr(), _axis_strides(c_hi), dst.data_ptr(),
-                _axis_strides(dst), lo, hi, ctypes.byref(tab), stream))
+            _launch(1, KID_AXIS_INV, (n,), c_lo, lib.mifwt_bwt_axis_inv, dt, L, outer, n, inner, c_lo.data_ptr(), _axis_strides(c_lo),
+                    c_hi.data_ptr(), _axis_strides(c_hi), dst.data_ptr(), _axis_strides(dst), lo, hi, ctypes.byref(tab))
         cur = out
     return y
 
@@ -385,10 +337,9 @@ def rows_tree(x: torch.Tensor, bk: Bank, k: int) -> List[torch.Tensor]:
     out = [torch.empty((r, n), dtype=x.dtype, device=x.device) for _ in range(k)]
     if r:
         dt = _engine._DTYPE_IDS[x.dtype]
-        ptrs = _engine._arr(ctypes.c_void_p, k)(*[t.data_ptr() for t in out])
-        lib, tab, xp, xs = _lib(), bk.tables(x.device), x.data_ptr(), x.stride(0) if r > 1 else n
-        lo, hi, L = _engine._taps_array(bk.f_lo), _engine._taps_array(bk.f_hi), bk.filt_len
-        _launch(0, KID_TREE_FWD, (n,), x, lambda stream: lib.mifwt_bwt_tree_fwd(dt, L, r, n, xs, k, xp, ptrs, lo, hi, ctypes.byref(tab), stream))
+        tab, xs = bk.tables(x.device), x.stride(0) if r > 1 else n
+        _launch(0, KID_TREE_FWD, (n,), x, _lib().mifwt_bwt_tree_fwd, dt, bk.filt_len, r, n, xs, k, x.data_ptr(), _engine._ptr_array(out),
+                _engine._taps_array(bk.f_lo), _engine._taps_array(bk.f_hi), ctypes.byref(tab))
     return [out[i].view(r, 1 << (i + 1), n >> (i + 1)) for i in range(k)]
 
 
@@ -402,11 +353,10 @@ def transposed_tree(leaves: torch.Tensor, bk: Bank, k: int) -> List[torch.Tensor
     out = [torch.empty((r, n), dtype=leaves.dtype, device=leaves.device) for _ in range(k)]
     if r:
         dt = _engine._DTYPE_IDS[leaves.dtype]
-        ptrs = _engine._arr(ctypes.c_void_p, k)(*[t.data_ptr() for t in out])
-        lib, tab, lp = _lib(), bk.tables(leaves.device), leaves.data_ptr()
+        tab = bk.tables(leaves.device)
         # (the C entry takes the filters in rec order and reverses them into row filters)
-        lo, hi, L = _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi), bk.filt_len
-        _launch(1, KID_TREE_INV, (n,), leaves, lambda stream: lib.mifwt_bwt_tree_inv(dt, L, r, n, k, lp, ptrs, lo, hi, ctypes.byref(tab), stream))
+        _launch(1, KID_TREE_INV, (n,), leaves, _lib().mifwt_bwt_tree_inv, dt, bk.filt_len, r, n, k, leaves.data_ptr(), _engine._ptr_array(out),
+                _engine._taps_array(bk.r_lo), _engine._taps_array(bk.r_hi), ctypes.byref(tab))
     return [out[i].view(r, 1 << i, n >> i) for i in range(k)]
 
 

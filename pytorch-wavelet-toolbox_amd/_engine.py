@@ -17,8 +17,6 @@ import torch
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, os.environ.get("MIFWT_LIB", "libmifwt.so"))  # (MIFWT_LIB: an experiment build next to the product library, tools/ only)
 if "MIFWT_LIB" in os.environ:
-    import warnings
-
     warnings.warn(f"ptwt_amd: MIFWT_LIB is set — running on the experiment build {LIB_PATH}, not on the product library", RuntimeWarning)
 ABI_VERSION = 3
 
@@ -56,12 +54,108 @@ class LevelDesc(ctypes.Structure):
     ]
 
 
+def _desc(ndim, dtype, mode_id, flen, batch, sig, sig_stride, coef, approx_stride, detail_stride) -> LevelDesc:
+    """A filled ``mifwt_level_desc``: extents per transformed axis, strides (elements) as (batch, axis 0, ..)."""
+    d = LevelDesc()
+    d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[dtype], mode_id, flen, batch
+    for a in range(ndim):
+        d.sig_extent[a], d.coef_extent[a] = int(sig[a]), int(coef[a])
+    for a in range(ndim + 1):
+        d.sig_stride[a], d.approx_stride[a], d.detail_stride[a] = sig_stride[a], approx_stride[a], detail_stride[a]
+    return d
+
+
+def _plane_strides(shape):
+    """(descriptor strides, plane stride) of the planes of a dense ``[B, 2^n, M_0.., pitch]`` level buffer."""
+    st = [1]
+    for n in reversed(shape[1:]):
+        st.insert(0, st[0] * n)
+    return (st[0], *st[2:]), st[1]
+
+
+def _dense_strides(extent):
+    """Strides of a dense ``[B, *extent]`` tensor that is never materialised."""
+    st = [1]
+    for n in reversed(extent):
+        st.insert(0, st[0] * int(n))
+    return st
+
+
 _lib: Optional[ctypes.CDLL] = None
+_has_kid_dtaps = False  # (decided when the library is loaded: an older experiment build reports id 0 for device taps)
+
+_c, _i64, _vp, _sz = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
+_dbl_p, _i64_p, _i32_p, _vpp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_vp)
+_vppp, _desc_p, _desc_pp = ctypes.POINTER(_vpp), ctypes.POINTER(LevelDesc), ctypes.POINTER(ctypes.POINTER(LevelDesc))
+_FROM_SIG = [_desc_p, _vp, _vp, _vpp]  # (signal, approximation, detail pointers): mifwt_dwt_fwd and the adjoint of mifwt_dwt_inv
+_FROM_COEF = [_desc_p, _vp, _vpp, _vp]  # (approximation, detail pointers, signal): mifwt_dwt_inv and the adjoint of mifwt_dwt_fwd
+_HOST_TAPS, _DEV_TAPS, _SCRATCH = [_dbl_p, _dbl_p], [_vp, _vp], [_vp, _sz, _vp]  # (.., scratch, its size, stream)
+_TAIL = [_c, _c, _c, _i64, _i64, _c, _vp, _i64, _vp, _i64, _vpp, _i64_p, _dbl_p, _dbl_p, _vp]
+_PYRAMID = [_c, _desc_pp, _vp, _vppp, _vp, _dbl_p, _dbl_p, _vp]
+
+# C ABI (include/mifwt.h): entry point -> (restype, argtypes).  load_library() applies the table; modules that call entries of their own
+# add them with register_entries().
+_ENTRIES: dict = {
+    "mifwt_strerror": (ctypes.c_char_p, [_c]),
+    "mifwt_set_option": (_c, [_c, _c]),
+    "mifwt_kernel_id": (_c, [_desc_p, _c]),
+    "mifwt_workspace_bytes": (_sz, [_desc_p, _c]),
+    "mifwt_dwt_fwd": (_c, _FROM_SIG + _HOST_TAPS + _SCRATCH),
+    "mifwt_dwt_inv": (_c, _FROM_COEF + _HOST_TAPS + _SCRATCH),
+    "mifwt_dwt_fwd_adjoint": (_c, _FROM_COEF + _HOST_TAPS + _SCRATCH),
+    "mifwt_dwt_inv_adjoint": (_c, _FROM_SIG + _HOST_TAPS + _SCRATCH),
+    "mifwt_tap_correlate": (_c, [_c, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _c, _c, _c, _c, _vp, _vp]),
+    "mifwt_tap_correlate_dilated": (_c, [_c, _i64, _i64, _vp, _i64, _vp, _i64, _c, _i64, _i64, _vp, _vp]),
+    "mifwt_dwt2_fwd_pair_supported": (_c, [_desc_p, _desc_p]),
+    "mifwt_dwt2_fwd_pair": (_c, [_desc_p, _desc_p, _vp, _vpp, _vp, _vpp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_dwt2_inv_pair_supported": (_c, [_desc_p, _desc_p]),
+    "mifwt_dwt2_inv_pair": (_c, [_desc_p, _desc_p, _vp, _vpp, _vpp, _vp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_dwt2_fwd_pyramid_supported": (_c, [_c, _desc_pp]),
+    "mifwt_dwt2_fwd_pyramid": (_c, _PYRAMID),
+    "mifwt_dwt2_inv_pyramid_supported": (_c, [_c, _desc_pp]),
+    "mifwt_dwt2_inv_pyramid": (_c, _PYRAMID),
+    "mifwt_dwt1_fwd_tail_max_n": (_c, [_c]),
+    "mifwt_dwt1_fwd_tail": (_c, _TAIL),
+    "mifwt_dwt1_fwd_long": (_c, _TAIL),
+    "mifwt_dwt1_fwd_long_levels": (_c, [_c, _c, _c, _i64, _i64, _c]),
+    "mifwt_dwt1_inv_long_supported": (_c, [_c, _c, _i64, _c, _i32_p]),
+    "mifwt_dwt1_inv_long": (_c, [_c, _c, _i64, _c, _i32_p, _vp, _i64, _vpp, _i64_p, _vp, _i64, _dbl_p, _dbl_p, _vp]),
+    "mifwt_dwt1_inv_tail": (_c, [_c, _c, _i64, _i64, _c, _vp, _i64, _vpp, _i64_p, _i32_p, _vp, _i64, _dbl_p, _dbl_p, _vp]),
+    # ---- the entries below may be missing from an older build that MIFWT_ALLOW_ABI_MISMATCH=1 accepted for a same-run comparison (tools/)
+    "mifwt_workspace_bytes_dtaps": (_sz, [_desc_p, _c]),
+    "mifwt_kernel_id_dtaps": (_c, [_desc_p, _c]),
+    "mifwt_dwt_fwd_dtaps": (_c, _FROM_SIG + _DEV_TAPS + _SCRATCH),
+    "mifwt_dwt_inv_dtaps": (_c, _FROM_COEF + _DEV_TAPS + _SCRATCH),
+    "mifwt_dwt_fwd_adjoint_dtaps": (_c, _FROM_COEF + _DEV_TAPS + _SCRATCH),
+    "mifwt_dwt_inv_adjoint_dtaps": (_c, _FROM_SIG + _DEV_TAPS + _SCRATCH),
+    "mifwt_launch_count": (ctypes.c_uint64, [_c]),
+    "mifwt_tap_correlate_planes": (_c, [_c, _c] + [_i64] * 5 + [_vp, _i64, _i64, _vp, _i64, _i64, _c, _c, _c, _c, _vp, _vp]),
+    "mifwt_dwt1_inv_outer": (_c, [_c] + [_i64] * 4 + [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _c, _dbl_p, _dbl_p, _vp, _vp, _vp]),
+    "mifwt_dwt1_fwd_outer": (_c, [_c, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _c, _c, _dbl_p, _dbl_p, _vp, _vp, _vp]),
+}
+_MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
+                   "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
+_abi_mismatch = False
+
+
+def _bind(lib, names) -> None:
+    for name in names:
+        if _abi_mismatch and name in _MAY_BE_MISSING and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _ENTRIES[name]
+
+
+def register_entries(table: dict) -> None:
+    """Entry points another module of the package calls itself: same table, bound with the rest (at once when the library is loaded)."""
+    _ENTRIES.update(table)
+    if _lib is not None:
+        _bind(_lib, table)
 
 
 def load_library() -> ctypes.CDLL:
     """Load libmifwt.so (once).  Fails loudly when the HIP extension has not been built."""
-    global _lib
+    global _lib, _has_kid_dtaps, _abi_mismatch
     if _lib is not None:
         return _lib
     if not os.path.isfile(LIB_PATH):
@@ -71,104 +165,20 @@ def load_library() -> ctypes.CDLL:
             "There is no CPU/eager fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    vp, cp = ctypes.c_void_p, ctypes.c_char_p
-    dbl_p = ctypes.POINTER(ctypes.c_double)
-    desc_p = ctypes.POINTER(LevelDesc)
     lib.mifwt_abi_version.restype = ctypes.c_int
     lib.mifwt_abi_version.argtypes = []
     # the version check comes BEFORE any other symbol is bound: a stale library then says "rebuild" instead of failing with an
     # AttributeError on the first entry point it lacks
-    mismatch = lib.mifwt_abi_version() != ABI_VERSION
-    if mismatch:
+    _abi_mismatch = lib.mifwt_abi_version() != ABI_VERSION
+    if _abi_mismatch:
         # (an experiment build loaded through MIFWT_LIB is held to the same check: its mifwt_level_desc / entry-point signatures must be
         # the ones declared above, or a call corrupts memory instead of failing; MIFWT_ALLOW_ABI_MISMATCH=1 is the explicit way around)
         if os.environ.get("MIFWT_ALLOW_ABI_MISMATCH") != "1":
             raise RuntimeError(f"ptwt_amd: {os.path.basename(LIB_PATH)} has ABI version {lib.mifwt_abi_version()}, this package expects "
                                f"{ABI_VERSION}; rebuild the extension (MIFWT_ALLOW_ABI_MISMATCH=1 loads it anyway, at your own risk)")
         warnings.warn("ptwt_amd: ABI version mismatch accepted through MIFWT_ALLOW_ABI_MISMATCH=1")
-    lib.mifwt_strerror.restype = cp
-    lib.mifwt_strerror.argtypes = [ctypes.c_int]
-    lib.mifwt_kernel_id.restype = ctypes.c_int
-    lib.mifwt_kernel_id.argtypes = [desc_p, ctypes.c_int]
-    lib.mifwt_workspace_bytes.restype = ctypes.c_size_t
-    lib.mifwt_workspace_bytes.argtypes = [desc_p, ctypes.c_int]
-    lib.mifwt_dwt_fwd.restype = ctypes.c_int
-    lib.mifwt_dwt_fwd.argtypes = [desc_p, vp, vp, ctypes.POINTER(vp), dbl_p, dbl_p, vp, ctypes.c_size_t, vp]
-    lib.mifwt_dwt_inv.restype = ctypes.c_int
-    lib.mifwt_dwt_inv.argtypes = [desc_p, vp, ctypes.POINTER(vp), vp, dbl_p, dbl_p, vp, ctypes.c_size_t, vp]
-    lib.mifwt_dwt_fwd_adjoint.restype = ctypes.c_int
-    lib.mifwt_dwt_fwd_adjoint.argtypes = [desc_p, vp, ctypes.POINTER(vp), vp, dbl_p, dbl_p, vp, ctypes.c_size_t, vp]
-    lib.mifwt_dwt_inv_adjoint.restype = ctypes.c_int
-    lib.mifwt_dwt_inv_adjoint.argtypes = [desc_p, vp, vp, ctypes.POINTER(vp), dbl_p, dbl_p, vp, ctypes.c_size_t, vp]
-    lib.mifwt_tap_correlate.restype = ctypes.c_int
-    lib.mifwt_tap_correlate.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, vp,
-                                        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
-    lib.mifwt_tap_correlate_dilated.restype = ctypes.c_int
-    lib.mifwt_tap_correlate_dilated.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64,
-                                                ctypes.c_int, ctypes.c_int64, ctypes.c_int64, vp, vp]
-    lib.mifwt_dwt2_fwd_pair_supported.restype = ctypes.c_int
-    lib.mifwt_dwt2_fwd_pair_supported.argtypes = [desc_p, desc_p]
-    lib.mifwt_dwt2_fwd_pair.restype = ctypes.c_int
-    lib.mifwt_dwt2_fwd_pair.argtypes = [desc_p, desc_p, vp, ctypes.POINTER(vp), vp, ctypes.POINTER(vp), dbl_p, dbl_p, vp]
-    vpp = ctypes.POINTER(vp)
-    lib.mifwt_dwt2_fwd_pyramid_supported.restype = ctypes.c_int
-    lib.mifwt_dwt2_fwd_pyramid_supported.argtypes = [ctypes.c_int, ctypes.POINTER(desc_p)]
-    lib.mifwt_dwt2_inv_pyramid_supported.restype = ctypes.c_int
-    lib.mifwt_dwt2_inv_pyramid_supported.argtypes = [ctypes.c_int, ctypes.POINTER(desc_p)]
-    lib.mifwt_dwt2_inv_pyramid.restype = ctypes.c_int
-    lib.mifwt_dwt2_inv_pyramid.argtypes = [ctypes.c_int, ctypes.POINTER(desc_p), vp, ctypes.POINTER(vpp), vp, dbl_p, dbl_p, vp]
-    lib.mifwt_dwt2_fwd_pyramid.restype = ctypes.c_int
-    lib.mifwt_dwt2_fwd_pyramid.argtypes = [ctypes.c_int, ctypes.POINTER(desc_p), vp, ctypes.POINTER(vpp), vp, dbl_p, dbl_p, vp]
-    lib.mifwt_dwt2_inv_pair_supported.restype = ctypes.c_int
-    lib.mifwt_dwt2_inv_pair_supported.argtypes = [desc_p, desc_p]
-    lib.mifwt_dwt2_inv_pair.restype = ctypes.c_int
-    lib.mifwt_dwt2_inv_pair.argtypes = [desc_p, desc_p, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, dbl_p, dbl_p, vp]
-    lib.mifwt_dwt1_fwd_tail_max_n.restype = ctypes.c_int
-    lib.mifwt_dwt1_fwd_tail_max_n.argtypes = [ctypes.c_int]
-    lib.mifwt_dwt1_fwd_tail.restype = ctypes.c_int
-    lib.mifwt_dwt1_fwd_tail.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, vp,
-                                        ctypes.c_int64, vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), dbl_p, dbl_p, vp]
-    lib.mifwt_dwt1_fwd_long.restype = ctypes.c_int
-    lib.mifwt_dwt1_fwd_long.argtypes = lib.mifwt_dwt1_fwd_tail.argtypes
-    lib.mifwt_dwt1_fwd_long_levels.restype = ctypes.c_int
-    lib.mifwt_dwt1_fwd_long_levels.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
-    lib.mifwt_dwt1_inv_long_supported.restype = ctypes.c_int
-    lib.mifwt_dwt1_inv_long_supported.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
-    lib.mifwt_dwt1_inv_long.restype = ctypes.c_int
-    lib.mifwt_dwt1_inv_long.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), vp, ctypes.c_int64,
-                                        ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), vp, ctypes.c_int64, dbl_p, dbl_p, vp]
-    lib.mifwt_dwt1_inv_tail.restype = ctypes.c_int
-    lib.mifwt_dwt1_inv_tail.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64,
-                                        ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), vp,
-                                        ctypes.c_int64, dbl_p, dbl_p, vp]
-    experiment = mismatch  # (tools/: an older build accepted for a same-run comparison may lack the newest entry points)
-    if not experiment or hasattr(lib, "mifwt_workspace_bytes_dtaps"):
-        lib.mifwt_workspace_bytes_dtaps.restype = ctypes.c_size_t
-        lib.mifwt_workspace_bytes_dtaps.argtypes = [desc_p, ctypes.c_int]
-    if not experiment or hasattr(lib, "mifwt_kernel_id_dtaps"):  # (round 6; an older experiment build: level_events report id 0 for device taps)
-        lib.mifwt_kernel_id_dtaps.restype = ctypes.c_int
-        lib.mifwt_kernel_id_dtaps.argtypes = [desc_p, ctypes.c_int]
-        for name in ("mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps", "mifwt_dwt_inv_adjoint_dtaps"):
-            getattr(lib, name).restype = ctypes.c_int
-        lib.mifwt_dwt_fwd_dtaps.argtypes = [desc_p, vp, vp, vpp, vp, vp, vp, ctypes.c_size_t, vp]
-        lib.mifwt_dwt_inv_dtaps.argtypes = [desc_p, vp, vpp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        lib.mifwt_dwt_fwd_adjoint_dtaps.argtypes = [desc_p, vp, vpp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        lib.mifwt_dwt_inv_adjoint_dtaps.argtypes = [desc_p, vp, vp, vpp, vp, vp, vp, ctypes.c_size_t, vp]
-    if not experiment or hasattr(lib, "mifwt_launch_count"):
-        lib.mifwt_launch_count.restype = ctypes.c_uint64
-        lib.mifwt_launch_count.argtypes = [ctypes.c_int]
-    if not experiment or hasattr(lib, "mifwt_tap_correlate_planes"):  # (round 6)
-        lib.mifwt_tap_correlate_planes.restype = ctypes.c_int
-        lib.mifwt_tap_correlate_planes.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 5 + [vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64,
-                                                   ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
-        lib.mifwt_dwt1_inv_outer.restype = ctypes.c_int
-        lib.mifwt_dwt1_inv_outer.argtypes = [ctypes.c_int] + [ctypes.c_int64] * 4 + [vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, vp,
-                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_int, dbl_p, dbl_p, vp, vp, vp]
-        lib.mifwt_dwt1_fwd_outer.restype = ctypes.c_int
-        lib.mifwt_dwt1_fwd_outer.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, ctypes.c_int64,
-                                             ctypes.c_int64, ctypes.c_int, ctypes.c_int, dbl_p, dbl_p, vp, vp, vp]
-    lib.mifwt_set_option.restype = ctypes.c_int
-    lib.mifwt_set_option.argtypes = [ctypes.c_int, ctypes.c_int]
+    _bind(lib, _ENTRIES)
+    _has_kid_dtaps = hasattr(lib, "mifwt_kernel_id_dtaps")
     _lib = lib
     return lib
 
@@ -187,8 +197,8 @@ def _require_gpu(t: torch.Tensor) -> None:
         )
 
 
-# Optional per-level device timing (bench.py's roofline leg): when set to a list, every level call
-# appends (tag, kernel_id, start_event, end_event) recorded on the launch stream.
+# Optional per-level device timing (bench.py's roofline leg): when set to a list, every launch
+# appends (tag, kernel_id, signal extent, start_event, end_event) recorded on the launch stream.
 level_events: Optional[list] = None
 
 ROW_ALIGN = int(os.environ.get("MIFWT_ROW_ALIGN", "1"))  # bytes; 1 = dense rows
@@ -248,20 +258,37 @@ class _Plan:
     the filled ``mifwt_level_desc``, the output allocation, scratch size and kernel id.  Cached, so a repeated
     call costs one ``torch.empty`` + one C call per level on the host."""
 
-    __slots__ = ("desc", "ref", "alloc_shape", "view_last", "nb", "plane_bytes", "ws_bytes", "kid", "empty")
+    __slots__ = ("desc", "ref", "extent", "alloc_shape", "view_last", "nb", "plane_bytes", "ws_bytes", "kid", "empty")
+
+    def __init__(self, d: LevelDesc, direction: Optional[int] = None, kid: int = 0, scratch: bool = True):
+        """``direction`` given: scratch size (unless ``scratch`` is false) and kernel id are the library's for that direction of
+        the level; None: a multi-level launch — no scratch, the kernel id of its route."""
+        self.desc, self.ref, self.extent = d, ctypes.byref(d), tuple(d.sig_extent[: d.ndim])
+        self.ws_bytes = _lib.mifwt_workspace_bytes(self.ref, direction) if direction is not None and scratch else 0
+        self.kid = kid if direction is None else _lib.mifwt_kernel_id(self.ref, direction)
+
+    def alloc(self, dtype, device) -> torch.Tensor:
+        """The level buffer (``device`` may be "meta"): rows of the padded pitch, viewed at their real length."""
+        buf = torch.empty(self.alloc_shape, dtype=dtype, device=device)
+        return buf if self.view_last is None else buf[..., : self.view_last]
 
 
 _plans: dict = {}
-
-
-def _trim_plans() -> None:
-    """Keep the plan cache bounded without dropping everything at once: past 4096 entries the oldest quarter goes (dicts keep
-    insertion order), so a caller that cycles through many geometries keeps its recent ones."""
-    if len(_plans) > 4096:
-        for k in list(_plans)[:1024]:
-            _plans.pop(k, None)
 _tls = threading.local()
 _taps_cache: dict = {}
+
+
+def _plan(key, build, cache: dict = _plans):
+    """The cached plan of ``key``, built on first use.  The cache stays bounded without dropping everything at once: past 4096 entries
+    the oldest quarter goes (dicts keep insertion order), so a caller that cycles through many geometries keeps its recent ones.
+    Cached plans are shared between threads and never own an array that a call writes."""
+    p = cache.get(key)
+    if p is None:
+        if len(cache) > 4096:
+            for k in list(cache)[:1024]:
+                cache.pop(k, None)
+        p = cache[key] = build()
+    return p
 
 
 class DevTaps:
@@ -307,14 +334,108 @@ def _taps_array(taps: Sequence[float]):
     return arr
 
 
+def _with_taps(lo, hi, entry=None, dtaps_name: Optional[str] = None):
+    """The one place that tells host taps from :class:`DevTaps`: (the entry point to call — ``entry`` for host taps, the library's
+    ``dtaps_name`` for device-resident ones —, whether they are device-resident, the two tap arguments: cached double arrays or
+    device pointers)."""
+    if isinstance(lo, DevTaps):
+        return dtaps_name and getattr(_lib, dtaps_name), True, lo.ptr, hi.ptr
+    return entry, False, _taps_array(lo), _taps_array(hi)
+
+
 def _band_ptrs(base: int, plane_bytes: int, n: int):
     """Device pointers of planes 1 .. n of a level buffer, in a fresh ctypes array: cached plans are shared between threads and
     ctypes releases the GIL during the C call, so a plan never owns an array that calls write to."""
     return _arr(ctypes.c_void_p, n)(*[base + s * plane_bytes for s in range(1, n + 1)])
 
 
-def _raw_stream(dev_index: int) -> int:
-    return torch._C._cuda_getCurrentRawStream(dev_index)
+def _ptr_array(tensors):
+    """The data pointers of ``tensors`` in a fresh ctypes array (per call, see :func:`_band_ptrs`)."""
+    return _arr(ctypes.c_void_p, len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _band_tables(key, n: int):
+    """``n`` arrays of three band pointers and the array of pointers to them, as the two pyramid entries take the detail bands of their
+    levels.  Per thread and reused: cached plans are shared between threads, and ctypes drops the GIL in the call; fresh ctypes arrays +
+    casts on every call are reference cycles that the garbage collector has to find: a 35 ms pause every few hundred calls
+    (tools/host_bound.py)."""
+    try:
+        return _tls.tables[key]
+    except (AttributeError, KeyError):
+        tables = _tls.__dict__.setdefault("tables", {})
+        if len(tables) > 256:
+            tables.clear()
+        rows = [_arr(ctypes.c_void_p, 3)() for _ in range(n)]
+        det = _arr(ctypes.POINTER(ctypes.c_void_p), n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_void_p)) for r in rows])
+        tables[key] = (rows, det)
+        return rows, det
+
+
+def _stream_of(t: torch.Tensor) -> int:
+    """The raw handle of the current stream of ``t``'s device."""
+    i = t.device.index
+    return torch._C._cuda_getCurrentRawStream(i if i is not None else torch.cuda.current_device())
+
+
+def _unit_last(t: torch.Tensor) -> torch.Tensor:
+    """``t`` with contiguous samples along its last axis (any other strides)."""
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+def _share_strides(tensors, unit_last: bool = False):
+    """The detail bands of a level as the C ABI takes them — one stride set for all of them (views into one level buffer have it; three
+    separate dense tensors have it), optionally with unit stride along the last axis: (``tensors`` itself or contiguous copies, their
+    strides)."""
+    ref = tensors[0].stride()
+    if (unit_last and ref[-1] != 1) or any(t.stride() != ref for t in tensors):
+        tensors = [t.contiguous() for t in tensors]
+        ref = tensors[0].stride()
+    return tensors, ref
+
+
+def _run(tag: str, kid: int, extent, anchor: torch.Tensor, entry, args: tuple, ws_bytes: Optional[int] = None, dtaps_ref=None,
+         direction: int = 0, may_refuse: bool = False) -> int:
+    """THE launch path: ``entry(*args, [scratch, scratch size,] stream)`` on the current stream of ``anchor``'s device (entered when
+    it is not the current one), timed with a pair of events when ``level_events`` is a list — it then gets ``(tag, kid, extent,
+    start, end)``.  ``ws_bytes``: the scratch the entry takes (None: it takes none).  ``dtaps_ref``: the descriptor reference of a
+    device-tap level — the fused 2-D kernels where they read device taps, else the generic passes, whose scratch differs from the
+    plan's route: ``mifwt_workspace_bytes_dtaps`` / ``mifwt_kernel_id_dtaps`` say which, for ``direction``.  ``may_refuse``:
+    MIFWT_ERR_UNSUPPORTED (-2) is an answer of this entry, not an error — it is returned, nothing was launched, nothing is recorded.
+    No host synchronisation: a device-tap call stays capturable into a graph."""
+    dev = anchor.device
+    if dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            return _run(tag, kid, extent, anchor, entry, args, ws_bytes, dtaps_ref, direction, may_refuse)
+    if ws_bytes is not None:
+        # the scratch block comes from the caching allocator on the launch stream, per launch; it returns there when `ws` dies, and
+        # the allocator only hands it to later work on the SAME stream (stream-ordered reuse), so the level that is still queued
+        # keeps it intact
+        if dtaps_ref is not None:
+            ws_bytes = int(_lib.mifwt_workspace_bytes_dtaps(dtaps_ref, direction))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        args = (*args, ws.data_ptr() if ws is not None else None, ws_bytes)
+    if level_events is None:
+        rc = entry(*args, _stream_of(anchor))
+    else:
+        stream = torch.cuda.current_stream(dev)
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record(stream)
+        rc = entry(*args, stream.cuda_stream)
+        ev[1].record(stream)
+        if rc != -2 or not may_refuse:
+            if dtaps_ref is not None:
+                kid = int(_lib.mifwt_kernel_id_dtaps(dtaps_ref, direction)) if _has_kid_dtaps else 0
+            level_events.append((tag, kid, tuple(extent), ev[0], ev[1]))
+    if rc != 0 and not (may_refuse and rc == -2):
+        _check(rc)
+    return rc
+
+
+def _enqueue(anchor: torch.Tensor, entry, *args) -> None:
+    """An entry that is not a level (tap correlations, single-axis passes): ``entry(*args, stream)`` inside ``anchor``'s device."""
+    with torch.cuda.device(anchor.device):
+        rc = entry(*args, _stream_of(anchor))
+    _check(rc)
 
 
 class HipLevelEngine:
@@ -322,7 +443,7 @@ class HipLevelEngine:
 
     @staticmethod
     def _analysis_plan(x: torch.Tensor, flen: int, mode_id: int, min_align: int = 1) -> _Plan:
-        lib = load_library()
+        load_library()
         ndim = x.dim() - 1
         batch = x.shape[0]
         sig = [int(n) for n in x.shape[1:]]
@@ -341,28 +462,12 @@ class HipLevelEngine:
         pitch = -(-coef[-1] * esz // align) * align // esz if align > esz and ndim >= 2 else coef[-1]
         if min_align < 0 and ndim >= 2:  # (experiments, tools/pitch_sweep.py: -k = k extra elements per row, whatever the alignment)
             pitch = coef[-1] - min_align
-        p = _Plan()
-        p.alloc_shape = (batch, nb, *coef[:-1], pitch)
-        p.view_last = coef[-1] if pitch != coef[-1] else None
-        p.nb = nb
-        p.empty = batch == 0 or min(coef) == 0
-        d = LevelDesc()
-        d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[x.dtype], mode_id, flen, batch
-        bstride = [1] * (ndim + 2)
-        for i in range(ndim, -1, -1):
-            bstride[i] = bstride[i + 1] * p.alloc_shape[i + 1]
-        for a in range(ndim):
-            d.sig_extent[a] = sig[a]
-            d.coef_extent[a] = coef[a]
-            d.sig_stride[1 + a] = x.stride(1 + a)
-            d.approx_stride[1 + a] = d.detail_stride[1 + a] = bstride[2 + a]
-        d.sig_stride[0] = x.stride(0)
-        d.approx_stride[0] = d.detail_stride[0] = bstride[0]
-        p.desc = d
-        p.ref = ctypes.byref(d)
-        p.plane_bytes = bstride[1] * esz
-        p.ws_bytes = 0 if p.empty else lib.mifwt_workspace_bytes(p.ref, 0)
-        p.kid = lib.mifwt_kernel_id(p.ref, 0)
+        alloc_shape = (batch, nb, *coef[:-1], pitch)
+        empty = batch == 0 or min(coef) == 0
+        planes, plane = _plane_strides(alloc_shape)
+        p = _Plan(_desc(ndim, x.dtype, mode_id, flen, batch, sig, x.stride(), coef, planes, planes), 0, scratch=not empty)
+        p.alloc_shape, p.view_last, p.nb, p.empty = alloc_shape, coef[-1] if pitch != coef[-1] else None, nb, empty
+        p.plane_bytes = plane * esz
         return p
 
     @staticmethod
@@ -370,14 +475,13 @@ class HipLevelEngine:
         """Copy of a level plan for a buffer WITHOUT the approximation plane ([B, 2^n - 1, M..]: plane s - 1 = band s): what a level of a
         multi-level launch gets whose approximation stays on chip (a [B, 2^n, M..] buffer would keep a dead plane alive as long as
         any of its detail bands lives).  The cached plan itself is shared with the per-level path and is not touched."""
-        q = _Plan()
         d = LevelDesc()
         ctypes.memmove(ctypes.addressof(d), ctypes.addressof(pl.desc), ctypes.sizeof(LevelDesc))
         plane = pl.desc.detail_stride[0] // pl.nb
         d.detail_stride[0] = d.approx_stride[0] = plane * (pl.nb - 1)
-        q.desc, q.ref = d, ctypes.byref(d)
+        q = _Plan(d, kid=pl.kid)
         q.alloc_shape = (pl.alloc_shape[0], pl.nb - 1, *pl.alloc_shape[2:])
-        q.view_last, q.nb, q.plane_bytes, q.ws_bytes, q.kid, q.empty = pl.view_last, pl.nb - 1, pl.plane_bytes, pl.ws_bytes, pl.kid, pl.empty
+        q.view_last, q.nb, q.plane_bytes, q.ws_bytes, q.empty = pl.view_last, pl.nb - 1, pl.plane_bytes, pl.ws_bytes, pl.empty
         return q
 
     def analysis(self, x: torch.Tensor, dec_lo: Sequence[float], dec_hi: Sequence[float], mode_id: int) -> torch.Tensor:
@@ -385,26 +489,14 @@ class HipLevelEngine:
         (bit (n-1-a) of s set <=> high-pass along axis a; plane 0 = approximation)."""
         _require_gpu(x)
         flen = len(dec_lo)
-        key = (x.shape, x.stride(), x.dtype, mode_id, flen, ROW_ALIGN)
-        p = _plans.get(key)
-        if p is None:
-            _trim_plans()
-            p = _plans[key] = self._analysis_plan(x, flen, mode_id)
-        buf = torch.empty(p.alloc_shape, dtype=x.dtype, device=x.device)
-        if p.view_last is not None:
-            buf = buf[..., : p.view_last]
+        p = _plan((x.shape, x.stride(), x.dtype, mode_id, flen, ROW_ALIGN), lambda: self._analysis_plan(x, flen, mode_id))
+        buf = p.alloc(x.dtype, x.device)
         if p.empty:
             return buf
         base = buf.data_ptr()
-        ptrs = _band_ptrs(base, p.plane_bytes, p.nb - 1)
-        lib = _lib
-        xp = x.data_ptr()
-        if _is_dev(dec_lo):
-            dl, dh = dec_lo.ptr, dec_hi.ptr
-            self._run(p, 0, x, lambda ws, wsb, stream: lib.mifwt_dwt_fwd_dtaps(p.ref, xp, base, ptrs, dl, dh, ws, wsb, stream), kid=0, dtaps=True)
-            return buf
-        lo, hi = _taps_array(dec_lo), _taps_array(dec_hi)
-        self._run(p, 0, x, lambda ws, wsb, stream: lib.mifwt_dwt_fwd(p.ref, xp, base, ptrs, lo, hi, ws, wsb, stream))
+        entry, dev, lo, hi = _with_taps(dec_lo, dec_hi, _lib.mifwt_dwt_fwd, "mifwt_dwt_fwd_dtaps")
+        _run("fwd", p.kid, p.extent, x, entry, (p.ref, x.data_ptr(), base, _band_ptrs(base, p.plane_bytes, p.nb - 1), lo, hi), p.ws_bytes,
+             p.ref if dev else None, 0)
         return buf
 
     def analysis_pair(self, x: torch.Tensor, dec_lo: Sequence[float], dec_hi: Sequence[float], mode_id: int):
@@ -416,43 +508,31 @@ class HipLevelEngine:
         if x.dim() != 3:
             return None
         flen = len(dec_lo)
-        key = ("pair", x.shape, x.stride(), x.dtype, mode_id, flen, ROW_ALIGN)
-        plan = _plans.get(key)
-        if plan is None:
-            _trim_plans()
+
+        def build():
             lib = load_library()
             p1 = self._analysis_plan(x, flen, mode_id)
             ok = False
             p2 = None
             if not p1.empty:
                 # geometry of the level-2 call: its input is plane 0 of the level-1 buffer (strides only, no memory)
-                lvl1 = torch.empty(p1.alloc_shape, dtype=x.dtype, device="meta")
-                if p1.view_last is not None:
-                    lvl1 = lvl1[..., : p1.view_last]
-                p2 = self._analysis_plan(lvl1[:, 0], flen, mode_id)
+                p2 = self._analysis_plan(p1.alloc(x.dtype, "meta")[:, 0], flen, mode_id)
                 ok = (not p2.empty) and bool(lib.mifwt_dwt2_fwd_pair_supported(p1.ref, p2.ref))
                 if ok:  # the first level's buffer: detail planes only (its approximation stays on chip)
                     lean = self._details_only(p1)
                     if lib.mifwt_dwt2_fwd_pair_supported(lean.ref, p2.ref):
                         p1 = lean
-            plan = _plans[key] = (p1, p2, ok)
-        p1, p2, ok = plan
+            return p1, p2, ok
+
+        p1, p2, ok = _plan(("pair", x.shape, x.stride(), x.dtype, mode_id, flen, ROW_ALIGN), build)
         if not ok:
             return None
-        buf1 = torch.empty(p1.alloc_shape, dtype=x.dtype, device=x.device)
-        buf2 = torch.empty(p2.alloc_shape, dtype=x.dtype, device=x.device)
-        if p1.view_last is not None:
-            buf1 = buf1[..., : p1.view_last]
-        if p2.view_last is not None:
-            buf2 = buf2[..., : p2.view_last]
+        buf1, buf2 = p1.alloc(x.dtype, x.device), p2.alloc(x.dtype, x.device)
         b1, b2 = buf1.data_ptr(), buf2.data_ptr()
         ptrs1 = _band_ptrs(b1 - (4 - p1.nb) * p1.plane_bytes, p1.plane_bytes, 3)  # band ad: plane 1 of a full buffer, plane 0 of a details-only one
         ptrs2 = _band_ptrs(b2, p2.plane_bytes, 3)
-        lo, hi = _taps_array(dec_lo), _taps_array(dec_hi)
-        lib = _lib
-        xp = x.data_ptr()
-        self._run(p1, 0, x, lambda ws, wsb, stream: lib.mifwt_dwt2_fwd_pair(p1.ref, p2.ref, xp, ptrs1, b2, ptrs2, lo, hi, stream),
-                  kid=KID_PAIR)
+        _run("fwd", KID_PAIR, p1.extent, x, _lib.mifwt_dwt2_fwd_pair,
+             (p1.ref, p2.ref, x.data_ptr(), ptrs1, b2, ptrs2, _taps_array(dec_lo), _taps_array(dec_hi)))
         return buf1, buf2
 
     def analysis_pyramid(self, x: torch.Tensor, dec_lo: Sequence[float], dec_hi: Sequence[float], mode_id: int, nlevels: int):
@@ -464,34 +544,17 @@ class HipLevelEngine:
         _require_gpu(x)
         if x.dim() != 3 or x.dtype != torch.float32:
             return None
-        flen = len(dec_lo)
-        key, plan = self._pyramid_plan(x, flen, mode_id, nlevels)
-        plans, n_ok, refs, kid = plan
+        key, (plans, n_ok, refs, kid) = self._pyramid_plan(x, len(dec_lo), mode_id, nlevels)
         if n_ok == 0:
             return None
-        bufs = []
-        for pl in plans:
-            b = torch.empty(pl.alloc_shape, dtype=x.dtype, device=x.device)
-            bufs.append(b if pl.view_last is None else b[..., : pl.view_last])
-        # the band-pointer arrays are per thread: cached plans are shared between threads, and ctypes drops the GIL in the call
-        skey = (key, n_ok)  # (a routing option may change how many levels the same geometry fuses)
-        slot = _tls.__dict__.setdefault("pyr", {}).get(skey)
-        if slot is None:
-            rows = [_arr(ctypes.c_void_p, 3)() for _ in plans]
-            det = _arr(ctypes.POINTER(ctypes.c_void_p), n_ok)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_void_p)) for r in rows])
-            slot = _tls.pyr[skey] = (rows, det)
-            if len(_tls.pyr) > 256:
-                _tls.pyr.clear()
-                _tls.pyr[skey] = slot
-        rows, det = slot
+        bufs = [pl.alloc(x.dtype, x.device) for pl in plans]
+        rows, det = _band_tables((key, n_ok), n_ok)  # (a routing option may change how many levels the same geometry fuses)
         for r, b, pl in zip(rows, bufs, plans):
             pb = pl.plane_bytes
             base = b.data_ptr() + (pl.nb - 3) * pb  # band ad: plane 1 of a full buffer, plane 0 of a details-only one
             r[0], r[1], r[2] = base, base + pb, base + 2 * pb
-        lo, hi = _taps_array(dec_lo), _taps_array(dec_hi)
-        lib = _lib
-        xp, ap = x.data_ptr(), bufs[-1].data_ptr()
-        self._run(plans[0], 0, x, lambda ws, wsb, stream: lib.mifwt_dwt2_fwd_pyramid(n_ok, refs, xp, det, ap, lo, hi, stream), kid=kid)
+        _run("fwd", kid, plans[0].extent, x, _lib.mifwt_dwt2_fwd_pyramid,
+             (n_ok, refs, x.data_ptr(), det, bufs[-1].data_ptr(), _taps_array(dec_lo), _taps_array(dec_hi)))
         return bufs
 
     def pyramid_levels(self, x: torch.Tensor, flen: int, mode_id: int, nlevels: int) -> int:
@@ -504,24 +567,24 @@ class HipLevelEngine:
     def _pyramid_plan(self, x: torch.Tensor, flen: int, mode_id: int, nlevels: int):
         """(cache key, (level plans, levels served, descriptor array, kernel id)) of :meth:`analysis_pyramid` for a geometry."""
         key = ("pyr", x.shape, x.stride(), mode_id, flen, min(nlevels, MAX_PYRAMID_LEVELS), ROW_ALIGN, PYRAMID_ROW_ALIGN)
-        plan = _plans.get(key)
-        if plan is None:
-            _trim_plans()
+        plan = _plans.get(key)  # (the lookup stays inline here: the headline call pays for every Python call in front of its launch)
+        if plan is not None:
+            return key, plan
+
+        def refs_of(plans):
+            return (ctypes.POINTER(LevelDesc) * len(plans))(*[ctypes.pointer(pl.desc) for pl in plans])
+
+        def build():
             lib = load_library()
 
             def chain(min_align):
                 plans = [self._analysis_plan(x, flen, mode_id, min_align)]
                 while len(plans) < min(nlevels, MAX_PYRAMID_LEVELS) and not plans[-1].empty:
-                    pl = plans[-1]
-                    lvl = torch.empty(pl.alloc_shape, dtype=x.dtype, device="meta")
-                    if pl.view_last is not None:
-                        lvl = lvl[..., : pl.view_last]
-                    plans.append(self._analysis_plan(lvl[:, 0], flen, mode_id, min_align))
+                    plans.append(self._analysis_plan(plans[-1].alloc(x.dtype, "meta")[:, 0], flen, mode_id, min_align))
                 n_ok, route = 0, 0
                 if not any(pl.empty for pl in plans):
                     for n in range(len(plans), 0, -1):
-                        refs = (ctypes.POINTER(LevelDesc) * n)(*[ctypes.pointer(pl.desc) for pl in plans[:n]])
-                        route = lib.mifwt_dwt2_fwd_pyramid_supported(n, refs)
+                        route = lib.mifwt_dwt2_fwd_pyramid_supported(n, refs_of(plans[:n]))
                         if route:
                             n_ok = n
                             break
@@ -537,16 +600,15 @@ class HipLevelEngine:
                 if n_a == n_ok and route_a == route:
                     plans = plans_a
             keep = plans[:n_ok]
-            refs = (ctypes.POINTER(LevelDesc) * n_ok)(*[ctypes.pointer(pl.desc) for pl in keep]) if n_ok else None
+            refs = refs_of(keep) if n_ok else None
             if n_ok > 1:  # every level but the last: detail planes only
                 lean = [self._details_only(pl) for pl in keep[:-1]] + [keep[-1]]
-                lrefs = (ctypes.POINTER(LevelDesc) * n_ok)(*[ctypes.pointer(pl.desc) for pl in lean])
+                lrefs = refs_of(lean)
                 if lib.mifwt_dwt2_fwd_pyramid_supported(n_ok, lrefs) == route:
                     keep, refs = lean, lrefs
-            if n_ok:
-                keep[0].ws_bytes = 0  # (the multi-level launches need no scratch; the plan's figure is that of the per-level route)
-            plan = _plans[key] = (keep, n_ok, refs, KID_SMALL if route == 2 else KID_PYRAMID)
-        return key, plan
+            return keep, n_ok, refs, KID_SMALL if route == 2 else KID_PYRAMID
+
+        return key, _plan(key, build)
 
     def analysis_tail(self, x: torch.Tensor, dec_lo: Sequence[float], dec_hi: Sequence[float], mode_id: int, nlevels: int):
         """The next levels of a 1-D decomposition in ONE launch — all ``nlevels`` remaining ones once a row fits into a workgroup (C
@@ -562,13 +624,14 @@ class HipLevelEngine:
         rows, n0 = x.shape
         if rows == 0 or n0 == 0 or flen > 32:
             return None
+        dt = _DTYPE_IDS[x.dtype]
         # rows too long for one workgroup, or too few rows to occupy the chip with one workgroup each: the chunked kernel fuses
         # as many levels as its halo rule allows (C ABI mifwt_dwt1_fwd_long), the caller comes back for the rest
-        k_long = lib.mifwt_dwt1_fwd_long_levels(_DTYPE_IDS[x.dtype], flen, mode_id, rows, n0, nlevels) if x.dtype == torch.float32 else 0
+        k_long = lib.mifwt_dwt1_fwd_long_levels(dt, flen, mode_id, rows, n0, nlevels) if x.dtype == torch.float32 else 0
         long_rows = k_long >= 2
         if long_rows:
             nlevels = k_long
-        elif n0 > lib.mifwt_dwt1_fwd_tail_max_n(_DTYPE_IDS[x.dtype]):
+        elif n0 > lib.mifwt_dwt1_fwd_tail_max_n(dt):
             return None
         sizes, n = [], n0
         for _ in range(nlevels):
@@ -581,72 +644,35 @@ class HipLevelEngine:
         esz = x.element_size()
         det = _arr(ctypes.c_void_p, nlevels)(*[b.data_ptr() + (sizes[i] * esz if i == last else 0) for i, b in enumerate(bufs)])
         det_rs = _arr(ctypes.c_int64, nlevels)(*[(2 if i == last else 1) * m for i, m in enumerate(sizes)])
-        lo, hi = _taps_array(dec_lo), _taps_array(dec_hi)
-        p = _Plan()
-        p.ws_bytes, p.kid = 0, (KID_LONG if long_rows else KID_TAIL)
-        d = LevelDesc()
-        d.ndim = 1
-        d.sig_extent[0] = n0
-        p.desc = d
-        xp, ap = x.data_ptr(), bufs[-1].data_ptr()
-        rc_box = []
-
-        def call(ws, wsb, stream):
-            entry = lib.mifwt_dwt1_fwd_long if long_rows else lib.mifwt_dwt1_fwd_tail
-            rc = entry(_DTYPE_IDS[x.dtype], flen, mode_id, rows, n0, nlevels, xp, x.stride(0), ap, 2 * sizes[-1], det, det_rs, lo, hi, stream)
-            rc_box.append(rc)
-            return 0 if rc == -2 else rc  # "unsupported" is an answer here, not an error
-
-        self._run(p, 0, x, call)
-        if rc_box and rc_box[0] == -2:
-            if level_events:  # (nothing was launched: the recorded event would claim a kernel that did not run)
-                level_events.pop()
-            return None
-        return bufs
+        # "unsupported" is an answer here, not an error
+        rc = _run("fwd", KID_LONG if long_rows else KID_TAIL, (n0,), x, lib.mifwt_dwt1_fwd_long if long_rows else lib.mifwt_dwt1_fwd_tail,
+                  (dt, flen, mode_id, rows, n0, nlevels, x.data_ptr(), x.stride(0), bufs[-1].data_ptr(), 2 * sizes[-1], det, det_rs,
+                   _taps_array(dec_lo), _taps_array(dec_hi)), may_refuse=True)
+        return None if rc == -2 else bufs
 
     def synthesis(self, approx: torch.Tensor, details: List[torch.Tensor], rec_lo: Sequence[float],
                   rec_hi: Sequence[float], out_extent: Sequence[int]) -> torch.Tensor:
         """``approx`` and the 2^n-1 ``details`` (band order): [B, M_0..] -> y [B, *out_extent] (dense)."""
         _require_gpu(approx)
         lib = load_library()
-        ndim = approx.dim() - 1
         flen = len(rec_lo)
         batch = approx.shape[0]
         y = torch.empty((batch, *out_extent), dtype=approx.dtype, device=approx.device)
         if y.numel() == 0:
             return y
-        ref_stride = details[0].stride()
-        if any(t.stride() != ref_stride for t in details):
-            details = [t.contiguous() for t in details]
-            ref_stride = details[0].stride()
-        key = ("inv", approx.shape, approx.stride(), ref_stride, approx.dtype, flen, tuple(out_extent))
-        p = _plans.get(key)
-        if p is None:
-            _trim_plans()
-            p = _Plan()
-            d = LevelDesc()
-            d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[approx.dtype], 0, flen, batch
-            for a in range(ndim):
-                d.sig_extent[a] = int(out_extent[a])
-                d.coef_extent[a] = int(approx.shape[1 + a])
-            for a in range(ndim + 1):
-                d.sig_stride[a] = y.stride(a)
-                d.approx_stride[a] = approx.stride(a)
-                d.detail_stride[a] = ref_stride[a]
-            p.desc = d
-            p.ref = ctypes.byref(d)
-            p.ws_bytes = lib.mifwt_workspace_bytes(p.ref, 1)
-            p.kid = lib.mifwt_kernel_id(p.ref, 1)
-            _plans[key] = p
-        ptrs = _arr(ctypes.c_void_p, len(details))(*[t.data_ptr() for t in details])
-        ap, yp = approx.data_ptr(), y.data_ptr()
-        if _is_dev(rec_lo):
-            dl, dh = rec_lo.ptr, rec_hi.ptr
-            self._run(p, 1, approx, lambda ws, wsb, stream: lib.mifwt_dwt_inv_dtaps(p.ref, ap, ptrs, yp, dl, dh, ws, wsb, stream), kid=0, dtaps=True)
-            return y
-        lo, hi = _taps_array(rec_lo), _taps_array(rec_hi)
-        self._run(p, 1, approx, lambda ws, wsb, stream: lib.mifwt_dwt_inv(p.ref, ap, ptrs, yp, lo, hi, ws, wsb, stream))
+        details, ref_stride = _share_strides(details)
+        p = _plan(("inv", approx.shape, approx.stride(), ref_stride, approx.dtype, flen, tuple(out_extent)),
+                  lambda: _Plan(_desc(approx.dim() - 1, approx.dtype, 0, flen, batch, out_extent, y.stride(), approx.shape[1:], approx.stride(),
+                                      ref_stride), 1))
+        entry, dev, lo, hi = _with_taps(rec_lo, rec_hi, lib.mifwt_dwt_inv, "mifwt_dwt_inv_dtaps")
+        _run("inv", p.kid, p.extent, approx, entry, (p.ref, approx.data_ptr(), _ptr_array(details), y.data_ptr(), lo, hi), p.ws_bytes,
+             p.ref if dev else None, 1)
         return y
+
+    def _tail_operands(self, approx: torch.Tensor, details: List[torch.Tensor]):
+        """Operands of the 1-D multi-level reconstructions with unit stride along the samples, the details' pointers and row strides."""
+        approx, details = _unit_last(approx), [_unit_last(t) for t in details]
+        return approx, _ptr_array(details), _arr(ctypes.c_int64, len(details))(*[t.stride(0) for t in details]), details
 
     def synthesis_tail(self, approx: torch.Tensor, details: List[torch.Tensor], rec_lo: Sequence[float], rec_hi: Sequence[float],
                        out_lens: Sequence[int]):
@@ -660,38 +686,18 @@ class HipLevelEngine:
         lib = load_library()
         flen = len(rec_lo)
         rows, m0 = approx.shape
-        cap = lib.mifwt_dwt1_fwd_tail_max_n(_DTYPE_IDS[approx.dtype])
+        dt = _DTYPE_IDS[approx.dtype]
+        cap = lib.mifwt_dwt1_fwd_tail_max_n(dt)
         if rows == 0 or m0 == 0 or flen > 32 or m0 > cap or max(out_lens) > cap or min(out_lens) < 1:
             return None
-        if approx.stride(1) != 1:
-            approx = approx.contiguous()
-        details = [t if t.stride(1) == 1 else t.contiguous() for t in details]
+        approx, det, det_rs, details = self._tail_operands(approx, details)
         y = torch.empty((rows, int(out_lens[-1])), dtype=approx.dtype, device=approx.device)
-        det = _arr(ctypes.c_void_p, nl)(*[t.data_ptr() for t in details])
-        det_rs = _arr(ctypes.c_int64, nl)(*[t.stride(0) for t in details])
         outs = (ctypes.c_int32 * nl)(*[int(v) for v in out_lens])
-        lo, hi = _taps_array(rec_lo), _taps_array(rec_hi)
-        p = _Plan()
-        p.ws_bytes, p.kid = 0, KID_INV_TAIL
-        d = LevelDesc()
-        d.ndim = 1
-        d.sig_extent[0] = int(out_lens[-1])
-        p.desc = d
-        ap, yp = approx.data_ptr(), y.data_ptr()
-        rc_box = []
-
-        def call(ws, wsb, stream):
-            rc = lib.mifwt_dwt1_inv_tail(_DTYPE_IDS[approx.dtype], flen, rows, m0, nl, ap, approx.stride(0), det, det_rs, outs, yp,
-                                         y.stride(0), lo, hi, stream)
-            rc_box.append(rc)
-            return 0 if rc == -2 else rc  # "unsupported" is an answer here, not an error
-
-        self._run(p, 1, approx, call)
-        if rc_box and rc_box[0] == -2:
-            if level_events:  # (nothing was launched, see analysis_tail)
-                level_events.pop()
-            return None
-        return y
+        # "unsupported" is an answer here, not an error
+        rc = _run("inv", KID_INV_TAIL, (int(out_lens[-1]),), approx, lib.mifwt_dwt1_inv_tail,
+                  (dt, flen, rows, m0, nl, approx.data_ptr(), approx.stride(0), det, det_rs, outs, y.data_ptr(), y.stride(0),
+                   _taps_array(rec_lo), _taps_array(rec_hi)), may_refuse=True)
+        return None if rc == -2 else y
 
     def synthesis_long(self, approx: torch.Tensor, details: List[torch.Tensor], rec_lo: Sequence[float], rec_hi: Sequence[float],
                        out_lens: Sequence[int]):
@@ -707,33 +713,23 @@ class HipLevelEngine:
         lib = load_library()
         flen = len(rec_lo)
         rows = approx.shape[0]
+        dt = _DTYPE_IDS[approx.dtype]
         lens = [int(approx.shape[1])] + [int(v) for v in out_lens]
         k = min(nl, 8)
         while k >= 2:
             m = (ctypes.c_int32 * (k + 1))(*lens[nl - k:])
-            if lib.mifwt_dwt1_inv_long_supported(_DTYPE_IDS[approx.dtype], flen, rows, k, m):
+            if lib.mifwt_dwt1_inv_long_supported(dt, flen, rows, k, m):
                 break
             k -= 1
         if k < 2:
             return None, 0
         if k < nl:
             return None, k
-        if approx.stride(1) != 1:
-            approx = approx.contiguous()
-        details = [t if t.stride(1) == 1 else t.contiguous() for t in details]
+        approx, det, det_rs, details = self._tail_operands(approx, details)
         y = torch.empty((rows, lens[-1]), dtype=approx.dtype, device=approx.device)
-        det = _arr(ctypes.c_void_p, nl)(*[t.data_ptr() for t in details])
-        det_rs = _arr(ctypes.c_int64, nl)(*[t.stride(0) for t in details])
-        lo, hi = _taps_array(rec_lo), _taps_array(rec_hi)
-        p = _Plan()
-        p.ws_bytes, p.kid = 0, KID_INV_LONG
-        d = LevelDesc()
-        d.ndim = 1
-        d.sig_extent[0] = lens[-1]
-        p.desc = d
-        ap, yp = approx.data_ptr(), y.data_ptr()
-        self._run(p, 1, approx, lambda ws, wsb, stream: lib.mifwt_dwt1_inv_long(_DTYPE_IDS[approx.dtype], flen, rows, nl, m, ap, approx.stride(0), det, det_rs, yp,
-                                                                              y.stride(0), lo, hi, stream))
+        _run("inv", KID_INV_LONG, (lens[-1],), approx, lib.mifwt_dwt1_inv_long,
+             (dt, flen, rows, nl, m, approx.data_ptr(), approx.stride(0), det, det_rs, y.data_ptr(), y.stride(0), _taps_array(rec_lo),
+              _taps_array(rec_hi)))
         return y, nl
 
     def synthesis_pair(self, approx2: torch.Tensor, details2: List[torch.Tensor], details1: List[torch.Tensor],
@@ -748,52 +744,21 @@ class HipLevelEngine:
         lib = load_library()
         flen = len(rec_lo)
         batch = approx2.shape[0]
-        st2 = details2[0].stride()
-        if any(t.stride() != st2 for t in details2):
-            details2 = [t.contiguous() for t in details2]
-            st2 = details2[0].stride()
-        st1 = details1[0].stride()
-        if any(t.stride() != st1 for t in details1):
-            details1 = [t.contiguous() for t in details1]
-            st1 = details1[0].stride()
+        (details2, st2), (details1, st1) = _share_strides(details2), _share_strides(details1)
         m1 = tuple(details1[0].shape[1:])
-        key = ("invpair", approx2.shape, approx2.stride(), st2, m1, st1, flen, tuple(out_extent))
-        plan = _plans.get(key)
-        if plan is None:
-            _trim_plans()
-            d2, d1 = LevelDesc(), LevelDesc()
-            for d in (d1, d2):
-                d.ndim, d.dtype, d.mode, d.filt_len, d.batch = 2, _DTYPE_IDS[approx2.dtype], 0, flen, batch
-            for a in range(2):
-                d2.sig_extent[a] = int(m1[a])
-                d2.coef_extent[a] = int(approx2.shape[1 + a])
-                d1.sig_extent[a] = int(out_extent[a])
-                d1.coef_extent[a] = int(m1[a])
-            ydense = [int(out_extent[0]) * int(out_extent[1]), int(out_extent[1]), 1]
-            lldense = [int(m1[0]) * int(m1[1]), int(m1[1]), 1]
-            for a in range(3):
-                d2.sig_stride[a] = lldense[a]       # never materialised
-                d2.approx_stride[a] = approx2.stride(a)
-                d2.detail_stride[a] = st2[a]
-                d1.sig_stride[a] = ydense[a]
-                d1.approx_stride[a] = lldense[a]    # ignored
-                d1.detail_stride[a] = st1[a]
-            p = _Plan()
-            p.desc = d1
-            p.ref = ctypes.byref(d1)
-            p.ws_bytes = 0
-            p.kid = KID_INV_PAIR
-            ok = bool(lib.mifwt_dwt2_inv_pair_supported(ctypes.byref(d2), p.ref))
-            plan = _plans[key] = (p, d2, ctypes.byref(d2), ok)
-        p, _d2, ref2, ok = plan
+
+        def build():
+            mid = _dense_strides(m1)  # the approximation between the two levels is never materialised (the finer level ignores its strides)
+            d2 = _desc(2, approx2.dtype, 0, flen, batch, m1, mid, approx2.shape[1:], approx2.stride(), st2)
+            p = _Plan(_desc(2, approx2.dtype, 0, flen, batch, out_extent, _dense_strides(out_extent), m1, mid, st1), kid=KID_INV_PAIR)
+            return p, d2, ctypes.byref(d2), bool(lib.mifwt_dwt2_inv_pair_supported(ctypes.byref(d2), p.ref))
+
+        p, _d2, ref2, ok = _plan(("invpair", approx2.shape, approx2.stride(), st2, m1, st1, flen, tuple(out_extent)), build)
         if not ok:
             return None
         y = torch.empty((batch, *out_extent), dtype=approx2.dtype, device=approx2.device)
-        ptrs2 = _arr(ctypes.c_void_p, 3)(*[t.data_ptr() for t in details2])  # per call: plans are shared between threads
-        ptrs1 = _arr(ctypes.c_void_p, 3)(*[t.data_ptr() for t in details1])
-        lo, hi = _taps_array(rec_lo), _taps_array(rec_hi)
-        ap, yp = approx2.data_ptr(), y.data_ptr()
-        self._run(p, 1, approx2, lambda ws, wsb, stream: lib.mifwt_dwt2_inv_pair(ref2, p.ref, ap, ptrs2, ptrs1, yp, lo, hi, stream))
+        _run("inv", p.kid, p.extent, approx2, lib.mifwt_dwt2_inv_pair,
+             (ref2, p.ref, approx2.data_ptr(), _ptr_array(details2), _ptr_array(details1), y.data_ptr(), _taps_array(rec_lo), _taps_array(rec_hi)))
         return y
 
     def synthesis_pyramid_plan(self, approx: torch.Tensor, levels: List[List[torch.Tensor]], flen: int, out_extent: Sequence[int]):
@@ -803,37 +768,24 @@ class HipLevelEngine:
         n = len(levels)
         if approx.dim() != 3 or approx.dtype != torch.float32 or n < 1 or n > MAX_PYRAMID_LEVELS:
             return None
-        batch = approx.shape[0]
         key = ("invpyr", approx.shape, approx.stride(), tuple((lv[0].shape, lv[0].stride()) for lv in levels), flen, tuple(out_extent))
-        plan = _plans.get(key)
-        if plan is None:
-            _trim_plans()
+        plan = _plans.get(key)  # (inline for the same reason as in _pyramid_plan)
+        if plan is not None:
+            return plan
+
+        def build():
             lib = load_library()
             descs = []
             for i, lv in enumerate(levels):
-                d = LevelDesc()
-                d.ndim, d.dtype, d.mode, d.filt_len, d.batch = 2, _DTYPE_IDS[approx.dtype], 0, flen, batch
                 m = lv[0].shape[1:]
                 out = levels[i + 1][0].shape[1:] if i + 1 < n else out_extent
-                for a in range(2):
-                    d.coef_extent[a] = int(m[a])
-                    d.sig_extent[a] = int(out[a])
-                dense = [int(m[0]) * int(m[1]), int(m[1]), 1]
-                ydense = [int(out[0]) * int(out[1]), int(out[1]), 1]
-                for a in range(3):
-                    d.sig_stride[a] = ydense[a]
-                    d.approx_stride[a] = approx.stride(a) if i == 0 else dense[a]
-                    d.detail_stride[a] = lv[0].stride(a)
-                descs.append(d)
+                descs.append(_desc(2, approx.dtype, 0, flen, approx.shape[0], out, _dense_strides(out), m,
+                                   approx.stride() if i == 0 else _dense_strides(m), lv[0].stride()))
             refs = (ctypes.POINTER(LevelDesc) * n)(*[ctypes.pointer(d) for d in descs])
             route = int(lib.mifwt_dwt2_inv_pyramid_supported(n, refs)) if tuple(approx.shape[1:]) == tuple(levels[0][0].shape[1:]) else 0
-            p = _Plan()
-            p.desc = descs[-1]
-            p.ref = ctypes.byref(descs[-1])
-            p.ws_bytes = 0
-            p.kid = KID_INV_SMALL if route == 1 else KID_INV_PYRAMID
-            plan = _plans[key] = (p, descs, refs, route)
-        return plan
+            return _Plan(descs[-1], kid=KID_INV_SMALL if route == 1 else KID_INV_PYRAMID), descs, refs, route
+
+        return _plan(key, build)
 
     def synthesis_pyramid(self, approx: torch.Tensor, levels: List[List[torch.Tensor]], rec_lo: Sequence[float],
                           rec_hi: Sequence[float], out_extent: Sequence[int], plan=None):
@@ -859,22 +811,11 @@ class HipLevelEngine:
                 return None
         n = len(levels)
         y = torch.empty((approx.shape[0], *out_extent), dtype=approx.dtype, device=approx.device)
-        # the band-pointer arrays are per thread and reused (cached plans are shared between threads, and ctypes drops the GIL in the
-        # call; fresh ctypes arrays + casts on every call are reference cycles that the garbage collector has to find: a 35 ms
-        # pause every few hundred calls, tools/host_bound.py)
-        slots = _tls.__dict__.setdefault("invpyr", {})
-        slot = slots.get(n)
-        if slot is None:
-            rows = [_arr(ctypes.c_void_p, 3)() for _ in range(n)]
-            det = _arr(ctypes.POINTER(ctypes.c_void_p), n)(*[ctypes.cast(r, ctypes.POINTER(ctypes.c_void_p)) for r in rows])
-            slot = slots[n] = (rows, det)
-        rows, det = slot
+        rows, det = _band_tables(n, n)
         for r, lv in zip(rows, levels):
             r[0], r[1], r[2] = lv[0].data_ptr(), lv[1].data_ptr(), lv[2].data_ptr()
-        lo, hi = _taps_array(rec_lo), _taps_array(rec_hi)
-        lib = _lib
-        ap, yp = approx.data_ptr(), y.data_ptr()
-        self._run(p, 1, approx, lambda ws, wsb, stream: lib.mifwt_dwt2_inv_pyramid(n, refs, ap, det, yp, lo, hi, stream))
+        _run("inv", p.kid, p.extent, approx, _lib.mifwt_dwt2_inv_pyramid,
+             (n, refs, approx.data_ptr(), det, y.data_ptr(), _taps_array(rec_lo), _taps_array(rec_hi)))
         return y
 
     # ---- adjoints (reverse-mode differentiation; C ABI mifwt_dwt_fwd_adjoint / mifwt_dwt_inv_adjoint) -------------
@@ -884,42 +825,22 @@ class HipLevelEngine:
         the level input, dense [B, *sig_shape]."""
         _require_gpu(g_buf)
         lib = load_library()
-        if g_buf.stride(-1) != 1:
-            g_buf = g_buf.contiguous()
-        ndim = g_buf.dim() - 2
+        g_buf = _unit_last(g_buf)
         flen = len(dec_lo)
         batch = g_buf.shape[0]
         g_x = torch.empty((batch, *sig_shape), dtype=g_buf.dtype, device=g_buf.device)
         if g_x.numel() == 0:
             return g_x
-        key = ("fwd_adj", g_buf.shape, g_buf.stride(), tuple(sig_shape), g_buf.dtype, mode_id, flen)
-        p = _plans.get(key)
-        if p is None:
-            p = _Plan()
-            d = LevelDesc()
-            d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[g_buf.dtype], mode_id, flen, batch
-            for a in range(ndim):
-                d.sig_extent[a] = int(sig_shape[a])
-                d.coef_extent[a] = int(g_buf.shape[2 + a])
-                d.sig_stride[1 + a] = g_x.stride(1 + a)
-                d.approx_stride[1 + a] = d.detail_stride[1 + a] = g_buf.stride(2 + a)
-            d.sig_stride[0] = g_x.stride(0)
-            d.approx_stride[0] = d.detail_stride[0] = g_buf.stride(0)
-            p.desc, p.ref = d, ctypes.byref(d)
-            p.nb = 1 << ndim
-            p.plane_bytes = g_buf.stride(1) * g_buf.element_size()
-            p.ws_bytes = lib.mifwt_workspace_bytes(p.ref, 2)
-            p.kid = lib.mifwt_kernel_id(p.ref, 2)
-            _plans[key] = p
+
+        def build():
+            planes = (g_buf.stride(0), *g_buf.stride()[2:])
+            return _Plan(_desc(g_buf.dim() - 2, g_buf.dtype, mode_id, flen, batch, sig_shape, g_x.stride(), g_buf.shape[2:], planes, planes), 2)
+
+        p = _plan(("fwd_adj", g_buf.shape, g_buf.stride(), tuple(sig_shape), g_buf.dtype, mode_id, flen), build)
         base = g_buf.data_ptr()
-        ptrs = _band_ptrs(base, p.plane_bytes, p.nb - 1)
-        gp = g_x.data_ptr()
-        if _is_dev(dec_lo):
-            dl, dh = dec_lo.ptr, dec_hi.ptr
-            self._run(p, 2, g_buf, lambda ws, wsb, stream: lib.mifwt_dwt_fwd_adjoint_dtaps(p.ref, base, ptrs, gp, dl, dh, ws, wsb, stream), kid=0, dtaps=True)
-            return g_x
-        lo, hi = _taps_array(dec_lo), _taps_array(dec_hi)
-        self._run(p, 2, g_buf, lambda ws, wsb, stream: lib.mifwt_dwt_fwd_adjoint(p.ref, base, ptrs, gp, lo, hi, ws, wsb, stream))
+        ptrs = _band_ptrs(base, g_buf.stride(1) * g_buf.element_size(), (1 << (g_buf.dim() - 2)) - 1)
+        entry, dev, lo, hi = _with_taps(dec_lo, dec_hi, lib.mifwt_dwt_fwd_adjoint, "mifwt_dwt_fwd_adjoint_dtaps")
+        _run("fwd_adj", p.kid, p.extent, g_buf, entry, (p.ref, base, ptrs, g_x.data_ptr(), lo, hi), p.ws_bytes, p.ref if dev else None, 2)
         return g_x
 
     def analysis_adjoint_bands(self, g_approx: torch.Tensor, g_details: Sequence[torch.Tensor], sig_shape: Sequence[int], dec_lo: Sequence[float],
@@ -929,46 +850,19 @@ class HipLevelEngine:
         level's adjoint, the details' gradients come from the caller one by one) — no concatenation; the C ABI takes a pointer per band."""
         _require_gpu(g_approx)
         lib = load_library()
-        if g_approx.stride(-1) != 1:
-            g_approx = g_approx.contiguous()
-        ref_stride = g_details[0].stride()
-        if ref_stride[-1] != 1 or any(t.stride() != ref_stride for t in g_details):
-            g_details = [t.contiguous() for t in g_details]
-        ndim = g_approx.dim() - 1
+        g_approx = _unit_last(g_approx)
+        g_details, gd_stride = _share_strides(g_details, unit_last=True)
         flen = len(dec_lo)
         batch = g_approx.shape[0]
         g_x = torch.empty((batch, *sig_shape), dtype=g_approx.dtype, device=g_approx.device)
         if g_x.numel() == 0:
             return g_x
-        gd0 = g_details[0]
-        key = ("fwd_adjb", g_approx.shape, g_approx.stride(), gd0.stride(), tuple(sig_shape), g_approx.dtype, mode_id, flen)
-        p = _plans.get(key)
-        if p is None:
-            p = _Plan()
-            d = LevelDesc()
-            d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[g_approx.dtype], mode_id, flen, batch
-            for a in range(ndim):
-                d.sig_extent[a] = int(sig_shape[a])
-                d.coef_extent[a] = int(g_approx.shape[1 + a])
-                d.sig_stride[1 + a] = g_x.stride(1 + a)
-                d.approx_stride[1 + a] = g_approx.stride(1 + a)
-                d.detail_stride[1 + a] = gd0.stride(1 + a)
-            d.sig_stride[0] = g_x.stride(0)
-            d.approx_stride[0] = g_approx.stride(0)
-            d.detail_stride[0] = gd0.stride(0)
-            p.desc, p.ref = d, ctypes.byref(d)
-            p.nb = 1 << ndim
-            p.ws_bytes = lib.mifwt_workspace_bytes(p.ref, 2)
-            p.kid = lib.mifwt_kernel_id(p.ref, 2)
-            _plans[key] = p
-        ptrs = _arr(ctypes.c_void_p, p.nb - 1)(*[t.data_ptr() for t in g_details])
-        ap, gp = g_approx.data_ptr(), g_x.data_ptr()
-        if _is_dev(dec_lo):
-            dl, dh = dec_lo.ptr, dec_hi.ptr
-            self._run(p, 2, g_approx, lambda ws, wsb, stream: lib.mifwt_dwt_fwd_adjoint_dtaps(p.ref, ap, ptrs, gp, dl, dh, ws, wsb, stream), kid=0, dtaps=True)
-            return g_x
-        lo, hi = _taps_array(dec_lo), _taps_array(dec_hi)
-        self._run(p, 2, g_approx, lambda ws, wsb, stream: lib.mifwt_dwt_fwd_adjoint(p.ref, ap, ptrs, gp, lo, hi, ws, wsb, stream))
+        p = _plan(("fwd_adjb", g_approx.shape, g_approx.stride(), gd_stride, tuple(sig_shape), g_approx.dtype, mode_id, flen),
+                  lambda: _Plan(_desc(g_approx.dim() - 1, g_approx.dtype, mode_id, flen, batch, sig_shape, g_x.stride(), g_approx.shape[1:],
+                                      g_approx.stride(), gd_stride), 2))
+        entry, dev, lo, hi = _with_taps(dec_lo, dec_hi, lib.mifwt_dwt_fwd_adjoint, "mifwt_dwt_fwd_adjoint_dtaps")
+        _run("fwd_adj", p.kid, p.extent, g_approx, entry, (p.ref, g_approx.data_ptr(), _ptr_array(g_details), g_x.data_ptr(), lo, hi), p.ws_bytes,
+             p.ref if dev else None, 2)
         return g_x
 
     def synthesis_adjoint(self, g_y: torch.Tensor, coef_shape: Sequence[int], rec_lo: Sequence[float],
@@ -977,8 +871,7 @@ class HipLevelEngine:
         ``s`` is the gradient of band ``s`` (plane 0: the approximation)."""
         _require_gpu(g_y)
         lib = load_library()
-        if g_y.stride(-1) != 1:
-            g_y = g_y.contiguous()
+        g_y = _unit_last(g_y)
         ndim = g_y.dim() - 1
         flen = len(rec_lo)
         batch = g_y.shape[0]
@@ -986,34 +879,16 @@ class HipLevelEngine:
         g_buf = torch.empty((batch, nb, *coef_shape), dtype=g_y.dtype, device=g_y.device)
         if g_buf.numel() == 0:
             return g_buf
-        key = ("inv_adj", g_y.shape, g_y.stride(), tuple(coef_shape), g_y.dtype, flen)
-        p = _plans.get(key)
-        if p is None:
-            p = _Plan()
-            d = LevelDesc()
-            d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[g_y.dtype], 0, flen, batch
-            for a in range(ndim):
-                d.sig_extent[a] = int(g_y.shape[1 + a])
-                d.coef_extent[a] = int(coef_shape[a])
-                d.sig_stride[1 + a] = g_y.stride(1 + a)
-                d.approx_stride[1 + a] = d.detail_stride[1 + a] = g_buf.stride(2 + a)
-            d.sig_stride[0] = g_y.stride(0)
-            d.approx_stride[0] = d.detail_stride[0] = g_buf.stride(0)
-            p.desc, p.ref = d, ctypes.byref(d)
-            p.nb = nb
-            p.plane_bytes = g_buf.stride(1) * g_buf.element_size()
-            p.ws_bytes = lib.mifwt_workspace_bytes(p.ref, 3)
-            p.kid = lib.mifwt_kernel_id(p.ref, 3)
-            _plans[key] = p
+
+        def build():
+            planes = (g_buf.stride(0), *g_buf.stride()[2:])
+            return _Plan(_desc(ndim, g_y.dtype, 0, flen, batch, g_y.shape[1:], g_y.stride(), coef_shape, planes, planes), 3)
+
+        p = _plan(("inv_adj", g_y.shape, g_y.stride(), tuple(coef_shape), g_y.dtype, flen), build)
         base = g_buf.data_ptr()
-        ptrs = _band_ptrs(base, p.plane_bytes, nb - 1)
-        yp = g_y.data_ptr()
-        if _is_dev(rec_lo):
-            dl, dh = rec_lo.ptr, rec_hi.ptr
-            self._run(p, 3, g_y, lambda ws, wsb, stream: lib.mifwt_dwt_inv_adjoint_dtaps(p.ref, yp, base, ptrs, dl, dh, ws, wsb, stream), kid=0, dtaps=True)
-            return g_buf
-        lo, hi = _taps_array(rec_lo), _taps_array(rec_hi)
-        self._run(p, 3, g_y, lambda ws, wsb, stream: lib.mifwt_dwt_inv_adjoint(p.ref, yp, base, ptrs, lo, hi, ws, wsb, stream))
+        ptrs = _band_ptrs(base, g_buf.stride(1) * g_buf.element_size(), nb - 1)
+        entry, dev, lo, hi = _with_taps(rec_lo, rec_hi, lib.mifwt_dwt_inv_adjoint, "mifwt_dwt_inv_adjoint_dtaps")
+        _run("inv_adj", p.kid, p.extent, g_y, entry, (p.ref, g_y.data_ptr(), base, ptrs, lo, hi), p.ws_bytes, p.ref if dev else None, 3)
         return g_buf
 
     def tap_correlate(self, a: torch.Tensor, b: torch.Tensor, filt_len: int, c0: int, sgn: int, mode_id: int,
@@ -1022,16 +897,10 @@ class HipLevelEngine:
         ``b`` [rows, N] (contiguous samples), ``out`` float64 [filt_len] on the same device, accumulated into."""
         _require_gpu(a)
         lib = load_library()
-        if a.stride(-1) != 1:
-            a = a.contiguous()
-        if b.stride(-1) != 1:
-            b = b.contiguous()
+        a, b = _unit_last(a), _unit_last(b)
         assert a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0] and out.dtype == torch.float64
-        with torch.cuda.device(a.device):
-            rc = lib.mifwt_tap_correlate(_DTYPE_IDS[a.dtype], a.shape[0], a.shape[1], b.shape[1], a.data_ptr(), a.stride(0),
-                                         b.data_ptr(), b.stride(0), filt_len, c0, sgn, mode_id, out.data_ptr(),
-                                         _raw_stream(a.device.index if a.device.index is not None else torch.cuda.current_device()))
-        _check(rc)
+        _enqueue(a, lib.mifwt_tap_correlate, _DTYPE_IDS[a.dtype], a.shape[0], a.shape[1], b.shape[1], a.data_ptr(), a.stride(0), b.data_ptr(),
+                 b.stride(0), filt_len, c0, sgn, mode_id, out.data_ptr())
 
     def tap_correlate_planes(self, along: int, a: torch.Tensor, b: torch.Tensor, filt_len: int, c0: int, sgn: int, mode_id: int,
                              out: torch.Tensor) -> None:
@@ -1041,16 +910,10 @@ class HipLevelEngine:
         C ABI ``mifwt_tap_correlate_planes``."""
         _require_gpu(a)
         lib = load_library()
-        if a.stride(-1) != 1:
-            a = a.contiguous()
-        if b.stride(-1) != 1:
-            b = b.contiguous()
+        a, b = _unit_last(a), _unit_last(b)
         assert a.dim() == 3 and b.dim() == 3 and a.shape[0] == b.shape[0] and a.dtype == b.dtype and out.dtype == torch.float64
-        with torch.cuda.device(a.device):
-            rc = lib.mifwt_tap_correlate_planes(_DTYPE_IDS[a.dtype], along, a.shape[0], a.shape[1], a.shape[2], b.shape[1], b.shape[2], a.data_ptr(),
-                                                a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), filt_len, c0, sgn, mode_id,
-                                                out.data_ptr(), _raw_stream(a.device.index if a.device.index is not None else torch.cuda.current_device()))
-        _check(rc)
+        _enqueue(a, lib.mifwt_tap_correlate_planes, _DTYPE_IDS[a.dtype], along, a.shape[0], a.shape[1], a.shape[2], b.shape[1], b.shape[2],
+                 a.data_ptr(), a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), filt_len, c0, sgn, mode_id, out.data_ptr())
 
     def analysis_outer(self, x: torch.Tensor, dec_lo, dec_hi, mode_id: int):
         """One 1-D analysis level along the MIDDLE axis of ``x`` [B, N, C] (unit stride along C, any batch / row strides) ->
@@ -1058,22 +921,15 @@ class HipLevelEngine:
         ``mifwt_dwt1_fwd_outer``); taps as host numbers or :class:`DevTaps`."""
         _require_gpu(x)
         lib = load_library()
-        if x.stride(-1) != 1:
-            x = x.contiguous()
+        x = _unit_last(x)
         B, N, C = x.shape
         flen = len(dec_lo)
         M = (N + flen - 1) // 2
         buf = torch.empty((B, 2, M, C), dtype=x.dtype, device=x.device)
         if B and N and C:
-            dev_taps = _is_dev(dec_lo)
-            lo = None if dev_taps else _taps_array(dec_lo)
-            hi = None if dev_taps else _taps_array(dec_hi)
-            with torch.cuda.device(x.device):
-                rc = lib.mifwt_dwt1_fwd_outer(_DTYPE_IDS[x.dtype], B, N, C, x.data_ptr(), x.stride(0), x.stride(1), buf.data_ptr(),
-                                              buf.data_ptr() + M * C * x.element_size(), 2 * M * C, C, mode_id, flen, lo, hi,
-                                              dec_lo.ptr if dev_taps else None, dec_hi.ptr if dev_taps else None,
-                                              _raw_stream(x.device.index if x.device.index is not None else torch.cuda.current_device()))
-            _check(rc)
+            _, dev, lo, hi = _with_taps(dec_lo, dec_hi)
+            _enqueue(x, lib.mifwt_dwt1_fwd_outer, _DTYPE_IDS[x.dtype], B, N, C, x.data_ptr(), x.stride(0), x.stride(1), buf.data_ptr(),
+                     buf.data_ptr() + M * C * x.element_size(), 2 * M * C, C, mode_id, flen, *((None, None, lo, hi) if dev else (lo, hi, None, None)))
         return buf[:, 0], buf[:, 1]
 
     def synthesis_outer(self, lo: torch.Tensor, hi: torch.Tensor, rec_lo, rec_hi, n_out: int) -> torch.Tensor:
@@ -1081,23 +937,14 @@ class HipLevelEngine:
         (C ABI ``mifwt_dwt1_inv_outer``); taps as host numbers or :class:`DevTaps`."""
         _require_gpu(lo)
         lib = load_library()
-        if lo.stride(-1) != 1:
-            lo = lo.contiguous()
-        if hi.stride(-1) != 1:
-            hi = hi.contiguous()
+        lo, hi = _unit_last(lo), _unit_last(hi)
         B, M, C = lo.shape
         flen = len(rec_lo)
         y = torch.empty((B, n_out, C), dtype=lo.dtype, device=lo.device)
         if B and M and C:
-            dev_taps = _is_dev(rec_lo)
-            tl = None if dev_taps else _taps_array(rec_lo)
-            th = None if dev_taps else _taps_array(rec_hi)
-            with torch.cuda.device(lo.device):
-                rc = lib.mifwt_dwt1_inv_outer(_DTYPE_IDS[lo.dtype], B, M, n_out, C, lo.data_ptr(), lo.stride(0), lo.stride(1), hi.data_ptr(), hi.stride(0),
-                                              hi.stride(1), y.data_ptr(), n_out * C, C, flen, tl, th, rec_lo.ptr if dev_taps else None,
-                                              rec_hi.ptr if dev_taps else None,
-                                              _raw_stream(lo.device.index if lo.device.index is not None else torch.cuda.current_device()))
-            _check(rc)
+            _, dev, tl, th = _with_taps(rec_lo, rec_hi)
+            _enqueue(lo, lib.mifwt_dwt1_inv_outer, _DTYPE_IDS[lo.dtype], B, M, n_out, C, lo.data_ptr(), lo.stride(0), lo.stride(1), hi.data_ptr(),
+                     hi.stride(0), hi.stride(1), y.data_ptr(), n_out * C, C, flen, *((None, None, tl, th) if dev else (tl, th, None, None)))
         return y
 
     def tap_correlate_dilated(self, a: torch.Tensor, b: torch.Tensor, filt_len: int, c0: int, tstep: int, out: torch.Tensor) -> None:
@@ -1105,70 +952,19 @@ class HipLevelEngine:
         gradients of the stationary levels; ``a``, ``b`` [rows, N] (contiguous samples), ``out`` float64 [filt_len]."""
         _require_gpu(a)
         lib = load_library()
-        if a.stride(-1) != 1:
-            a = a.contiguous()
-        if b.stride(-1) != 1:
-            b = b.contiguous()
+        a, b = _unit_last(a), _unit_last(b)
         assert a.dim() == 2 and a.shape == b.shape and out.dtype == torch.float64
-        with torch.cuda.device(a.device):
-            rc = lib.mifwt_tap_correlate_dilated(_DTYPE_IDS[a.dtype], a.shape[0], a.shape[1], a.data_ptr(), a.stride(0), b.data_ptr(),
-                                                 b.stride(0), filt_len, c0, tstep, out.data_ptr(),
-                                                 _raw_stream(a.device.index if a.device.index is not None else torch.cuda.current_device()))
-        _check(rc)
-
-    @staticmethod
-    def _run(p: _Plan, direction: int, anchor: torch.Tensor, call, kid: Optional[int] = None, dtaps: bool = False) -> None:
-        dev = anchor.device
-        if dev.index is not None and dev.index != torch.cuda.current_device():
-            with torch.cuda.device(dev):
-                return HipLevelEngine._run(p, direction, anchor, call, kid, dtaps)
-        # (device-resident taps: the fused 2-D kernels where they read device taps, else the generic passes — whose scratch differs
-        # from the plan's route; mifwt_kernel_id_dtaps says which)
-        wsb = int(_lib.mifwt_workspace_bytes_dtaps(p.ref, direction)) if dtaps else p.ws_bytes
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        if level_events is None:
-            rc = call(ws.data_ptr() if ws is not None else None, wsb, _raw_stream(dev.index if dev.index is not None else torch.cuda.current_device()))
-        else:
-            stream = torch.cuda.current_stream(dev)
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record(stream)
-            rc = call(ws.data_ptr() if ws is not None else None, wsb, stream.cuda_stream)
-            ev[1].record(stream)
-            d = p.desc
-            kid_run = (int(_lib.mifwt_kernel_id_dtaps(p.ref, direction)) if hasattr(_lib, "mifwt_kernel_id_dtaps") else 0) if dtaps else (p.kid if kid is None else kid)
-            level_events.append((("fwd", "inv", "fwd_adj", "inv_adj")[direction], kid_run, tuple(d.sig_extent[: d.ndim]), ev[0], ev[1]))
-        if rc != 0:
-            _check(rc)
-        # the scratch block returns to the caching allocator when `ws` dies; the allocator only hands it to
-        # later work on the SAME stream (stream-ordered reuse), so the level that is still queued keeps it intact
+        _enqueue(a, lib.mifwt_tap_correlate_dilated, _DTYPE_IDS[a.dtype], a.shape[0], a.shape[1], a.data_ptr(), a.stride(0), b.data_ptr(),
+                 b.stride(0), filt_len, c0, tstep, out.data_ptr())
 
 
 def kernel_id(ndim: int, dtype: torch.dtype, mode: str, filt_len: int, batch: int, sig_extent: Sequence[int],
               direction: int = 0) -> int:
     """Which kernel family a dense, default-layout level of this geometry dispatches to (0 = generic)."""
-    lib = load_library()
-    d = LevelDesc()
-    d.ndim, d.dtype, d.mode, d.filt_len, d.batch = ndim, _DTYPE_IDS[dtype], MODE_IDS[mode], filt_len, batch
-    if direction == 0:
-        coef = [(n + filt_len - 1) // 2 for n in sig_extent]
-        sig = list(sig_extent)
-    else:
-        sig = list(sig_extent)
-        coef = [(n + filt_len - 1) // 2 for n in sig_extent]
-    st = 1
-    for a in reversed(range(ndim)):
-        d.sig_extent[a], d.coef_extent[a] = sig[a], coef[a]
-    s = 1
-    for a in reversed(range(ndim)):
-        d.sig_stride[1 + a] = s
-        s *= sig[a]
-    d.sig_stride[0] = s
-    s = 1
-    for a in reversed(range(ndim)):
-        d.approx_stride[1 + a] = d.detail_stride[1 + a] = s
-        s *= coef[a]
-    d.approx_stride[0] = d.detail_stride[0] = s * (1 << ndim)
-    return lib.mifwt_kernel_id(ctypes.byref(d), direction)
+    coef = [(n + filt_len - 1) // 2 for n in sig_extent]
+    planes = _plane_strides((batch, 1 << ndim, *coef))[0]
+    d = _desc(ndim, dtype, MODE_IDS[mode], filt_len, batch, sig_extent, _dense_strides(sig_extent), coef, planes, planes)
+    return load_library().mifwt_kernel_id(ctypes.byref(d), direction)
 
 
 ENGINE = HipLevelEngine()

@@ -19,31 +19,12 @@ from .constants import Wavelet, supported_dtypes
 
 __all__ = ["swt", "iswt"]
 
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = _engine.load_library()
-    if not _bound:
-        vp, i64, dbl_p = ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)
-        lib.mifwt_swt_fwd.restype = ctypes.c_int
-        lib.mifwt_swt_fwd.argtypes = [ctypes.c_int, ctypes.c_int, i64, i64, i64, vp, i64, vp, vp, i64, i64, dbl_p, dbl_p,
-                                      ctypes.c_double, vp]
-        lib.mifwt_swt_inv.restype = ctypes.c_int
-        lib.mifwt_swt_inv.argtypes = [ctypes.c_int, ctypes.c_int, i64, i64, i64, vp, vp, i64, i64, vp, i64, dbl_p, dbl_p,
-                                      ctypes.c_double, vp]
-        _bound = True
-    return lib
-
-
-def _stream(t: torch.Tensor) -> int:
-    return _engine._raw_stream(t.device.index if t.device.index is not None else torch.cuda.current_device())
-
-
-def _rows(t: torch.Tensor) -> torch.Tensor:
-    """[B, N] with contiguous samples (row stride free)."""
-    return t if t.stride(-1) == 1 else t.contiguous()
+_i64, _vp, _dbl_p = ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
+_engine.register_entries({
+    "mifwt_swt_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _dbl_p, _dbl_p, ctypes.c_double, _vp]),
+    "mifwt_swt_inv": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _dbl_p, _dbl_p, ctypes.c_double, _vp]),
+})
+_rows = _engine._unit_last  # [B, N] with contiguous samples (row stride free)
 
 
 def _level_fwd(x: torch.Tensor, lo: Sequence[float], hi: Sequence[float], dilation: int, scale: float) -> torch.Tensor:
@@ -54,11 +35,8 @@ def _level_fwd(x: torch.Tensor, lo: Sequence[float], hi: Sequence[float], dilati
     buf = torch.empty((b, 2, n), dtype=x.dtype, device=x.device)
     if buf.numel() == 0:
         return buf
-    with torch.cuda.device(x.device):
-        rc = _lib().mifwt_swt_fwd(_engine._DTYPE_IDS[x.dtype], len(lo), b, n, dilation, x.data_ptr(), x.stride(0),
-                                  buf.data_ptr(), buf.data_ptr() + n * buf.element_size(), 2 * n, 2 * n,
-                                  _engine._taps_array(lo), _engine._taps_array(hi), scale, _stream(x))
-    _engine._check(rc)
+    _engine._enqueue(x, _engine.load_library().mifwt_swt_fwd, _engine._DTYPE_IDS[x.dtype], len(lo), b, n, dilation, x.data_ptr(), x.stride(0),
+                     buf.data_ptr(), buf.data_ptr() + n * buf.element_size(), 2 * n, 2 * n, _engine._taps_array(lo), _engine._taps_array(hi), scale)
     return buf
 
 
@@ -70,11 +48,8 @@ def _level_inv(a: torch.Tensor, d: torch.Tensor, lo: Sequence[float], hi: Sequen
     y = torch.empty((b, n), dtype=a.dtype, device=a.device)
     if y.numel() == 0:
         return y
-    with torch.cuda.device(a.device):
-        rc = _lib().mifwt_swt_inv(_engine._DTYPE_IDS[a.dtype], len(lo), b, n, dilation, a.data_ptr(), d.data_ptr(),
-                                  a.stride(0), d.stride(0), y.data_ptr(), n, _engine._taps_array(lo),
-                                  _engine._taps_array(hi), scale, _stream(a))
-    _engine._check(rc)
+    _engine._enqueue(a, _engine.load_library().mifwt_swt_inv, _engine._DTYPE_IDS[a.dtype], len(lo), b, n, dilation, a.data_ptr(), d.data_ptr(),
+                     a.stride(0), d.stride(0), y.data_ptr(), n, _engine._taps_array(lo), _engine._taps_array(hi), scale)
     return y
 
 
