@@ -318,6 +318,31 @@ int mifwt_swt_inv(int dtype, int filt_len, int64_t rows, int64_t n, int64_t dila
                   int64_t a_row_stride, int64_t d_row_stride, void* y, int64_t y_row_stride, const double* rec_lo,
                   const double* rec_hi, double scale, void* stream);
 
+/* 2-D stationary levels (swt2 / iswt2 of the package: the level above along both axes of a plane, pywt.swt2 with trim_approx=True,
+ * norm=False) in ONE launch per level that reads its input planes once and writes its outputs once (kernel ids 34 / 35,
+ * csrc/mifwt_swt2.hip: a walk down the a-trous lattice with a register ring of L row pairs; no intermediate plane, no transpose).
+ * `images` planes of H rows of W contiguous samples; every plane has its own image and row stride in elements (level j + 1 can read
+ * the cA plane of level j's buffer, slices need no copy); outputs must not overlap inputs.  Periodic in both axes with any number of
+ * wraps (any H, W >= 1, any dilation >= 1).  row_* filter along W (axis -1), col_* along H (axis -2); `scale` multiplies the result: 1
+ * for swt2, 0.25 for iswt2; with all four filters reversed and the same scale each call is the adjoint of the other.
+ *   fwd: p_lo/hi[r][n] = sum_t row_lo/hi[t] x[r][(n + D (L/2 - t)) mod W],   bands[0..3] = cA, cH, cV, cD with
+ *        cA = scale sum_m col_lo[m] p_lo[(r + D (L/2 - m)) mod H][n], cH = (col_hi, p_lo), cV = (col_lo, p_hi), cD = (col_hi, p_hi)
+ *   inv: bands[0..3] = cA, cH, cV, cD;  U[r][n] = sum_t row_lo[t] cA[r][(n + D (L/2 - 1 - t)) mod W] + row_hi[t] cV[r][..],
+ *        V likewise from (cH, cD),  y[r][n] = scale sum_m col_lo[m] U[(r + D (L/2 - 1 - m)) mod H][n] + col_hi[m] V[..][n]
+ * LIMIT: the ring lives in registers, so only the unrolled lengths exist: even filt_len 2 .. 20, f32 / f64, extents and
+ * dilation * filt_len below 2^28.  mifwt_swt2_supported answers 1 where the two entries run and 0 where they answer
+ * MIFWT_ERR_UNSUPPORTED (longer filters, f16): the caller then composes the level from mifwt_swt_fwd / mifwt_swt_inv.
+ * MIFWT_OPT_ROWS_PER_CHUNK > 0 overrides the lattice rows per wave. */
+int mifwt_swt2_supported(int dtype, int filt_len, int64_t images, int64_t H, int64_t W, int64_t dilation);
+int mifwt_swt2_fwd(int dtype, int filt_len, int64_t images, int64_t H, int64_t W, int64_t dilation, const void* x,
+                   int64_t x_image_stride, int64_t x_row_stride, void* const* bands, const int64_t* band_image_strides,
+                   const int64_t* band_row_strides, const double* row_lo, const double* row_hi, const double* col_lo,
+                   const double* col_hi, double scale, void* stream);
+int mifwt_swt2_inv(int dtype, int filt_len, int64_t images, int64_t H, int64_t W, int64_t dilation, const void* const* bands,
+                   const int64_t* band_image_strides, const int64_t* band_row_strides, void* y, int64_t y_image_stride,
+                   int64_t y_row_stride, const double* row_lo, const double* row_hi, const double* col_lo, const double* col_hi,
+                   double scale, void* stream);
+
 /* BOUNDARY-WAVELET levels — the padding-free transforms ptwt.MatrixWavedec / MatrixWaverec (src/ptwt/matmul_transform.py:409-430: pad one
  * sample if odd + torch.sparse.mm(A, x) + split; :679-703: cat + torch.sparse.mm(S, c) + drop the pad sample) and, in their separable
  * form, MatrixWavedec2 / MatrixWaverec2 (src/ptwt/matmul_transform_2.py:514-529: A_rows X A_cols^T through two transposes + splits;
@@ -495,11 +520,15 @@ int mifwt_set_option(int key, int value);
 int mifwt_pyr_profile_buffer(void* device_buffer);
 
 /* Diagnostic: how many launches of a kernel VARIANT this process has enqueued — variants that share a kernel id (what the tests use to
- * pin "this code path ran"; `variant` out of range: 0). */
+ * pin "this code path ran"; `variant` out of range: 0).  Values below 16 are variants; the 2-D stationary kernels, which have no
+ * variants, are counted under their kernel ids. */
 #define MIFWT_VARIANT_FWD_MFMA_WALK 0 /* id 11: the analysis kernel that walks down column panels */
 #define MIFWT_VARIANT_FWD_MFMA_TILE 1 /* id 11: the tile-at-a-time analysis kernel of round 2 (MIFWT_OPT_MFMA_MODE 3) */
 #define MIFWT_VARIANT_FWD_PYR_ST16 2  /* id 16: 16-byte stores after a lane-pair exchange (planes with 16-byte aligned rows) */
 #define MIFWT_VARIANT_FWD_PYR_ST8 3   /* id 16: 8-byte stores (any row pitch) */
+#define MIFWT_KERNEL_SWT2_FWD 34       /* id 34: fused 2-D stationary analysis level (mifwt_swt2_fwd) */
+#define MIFWT_KERNEL_SWT2_INV 35       /* id 35: fused 2-D stationary synthesis level (mifwt_swt2_inv) */
+#define MIFWT_LAUNCH_COUNTERS 64
 unsigned long long mifwt_launch_count(int variant);
 
 const char* mifwt_strerror(int code);

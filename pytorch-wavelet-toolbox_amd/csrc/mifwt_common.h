@@ -33,7 +33,7 @@ constexpr bool kDiag = false;
 // second barrier, bits 19 / 20 = kernel 16 without its tail wave / in its sixteen-wave form
 constexpr int kRouteBits = 8 | 64 | 512 | 1024 | 4096 | 8192 | 524288 | 1048576 | 2097152;
 inline int exp_word() { return kDiag ? g_options[MIFWT_OPT_EXP] : 0; }
-extern unsigned long long g_launch_counts[16];  // mifwt_launch_count(): launches per kernel variant (MIFWT_VARIANT_*)
+extern unsigned long long g_launch_counts[MIFWT_LAUNCH_COUNTERS];  // mifwt_launch_count(): launches per kernel variant (MIFWT_VARIANT_*)
 inline void count_launch(int variant) { __atomic_fetch_add(&g_launch_counts[variant], 1ull, __ATOMIC_RELAXED); }
 
 // Two-level batch of the LDS-tile 2-D analysis kernel (dwt2_fwd_tile; the 3-D composed route hands every slice of every volume to one

@@ -1,29 +1,58 @@
-"""Stationary (undecimated) wavelet transform: ``swt`` / ``iswt`` (API of reference src/ptwt/stationary_transform.py).
+"""Stationary (undecimated) wavelet transform: ``swt`` / ``iswt`` (API of reference src/ptwt/stationary_transform.py) and their 2-D
+forms ``swt2`` / ``iswt2`` (``pywt.swt2`` / ``pywt.iswt2``; the reference has none).
 
 Equivalent to ``pywt.swt(..., trim_approx=True, norm=False)`` like the reference.  Each level is one HIP kernel
 (C ABI ``mifwt_swt_fwd`` / ``mifwt_swt_inv``): stride-1 filter bank with dilation ``2^level`` and the periodic
 extension as an index map — the reference's ``_circular_pad`` + ``F.conv1d(dilation)`` + ``split`` (:95-107) and
 ``stack`` + ``_circular_pad`` + grouped ``F.conv_transpose1d`` + ``mean`` (:142-156).  Differentiable w.r.t. the data
 (each level kernel is the other's adjoint with reversed taps).
+
+A 2-D level is the 1-D level along both axes of a plane.  It runs as ONE fused launch (C ABI ``mifwt_swt2_fwd`` / ``mifwt_swt2_inv``,
+csrc/mifwt_swt2.hip: 1 plane in and 4 out, no intermediate plane, no transposed copy) where ``mifwt_swt2_supported`` says so, and
+otherwise — filters longer than 20 taps, learnable filter banks — on the COMPOSED route: the 1-D level ops along the last axis, then
+along the other one on permuted copies.  ``FORCE_COMPOSED`` selects that route for every call (cross-checks, timing baseline).
 """
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence, Union
+import math
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _engine, _fwt
 from ._wavelets import host_taps
-from .constants import Wavelet, supported_dtypes
+from .constants import Wavelet, WaveletCoeff2d, WaveletDetailTuple2d
 
-__all__ = ["swt", "iswt"]
+__all__ = ["swt", "iswt", "swt2", "iswt2"]
 
 _i64, _vp, _dbl_p = ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
+_vp4, _i64x4 = ctypes.c_void_p * 4, ctypes.c_int64 * 4
 _engine.register_entries({
     "mifwt_swt_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _dbl_p, _dbl_p, ctypes.c_double, _vp]),
     "mifwt_swt_inv": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _dbl_p, _dbl_p, ctypes.c_double, _vp]),
 })
+# The entries of the fused 2-D levels are registered when the first 2-D level asks for them (``_swt2_entries``): the record of engine
+# calls (tests/golden/engine_calls.json) lists the signature of every entry the package binds at import and a recorded case for every
+# launch entry among them, and these three are not part of that record.
+_SWT2_LAUNCHES = {
+    "mifwt_swt2_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64]),
+    "mifwt_swt2_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp4, _i64x4, _i64x4,
+                                      _dbl_p, _dbl_p, _dbl_p, _dbl_p, ctypes.c_double, _vp]),
+    "mifwt_swt2_inv": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64, _vp4, _i64x4, _i64x4, _vp, _i64, _i64,
+                                      _dbl_p, _dbl_p, _dbl_p, _dbl_p, ctypes.c_double, _vp]),
+}
+
+
+def _swt2_entries():
+    """The loaded library with ``mifwt_swt2_supported`` / ``_fwd`` / ``_inv`` bound (through ``_engine.register_entries``, once)."""
+    lib = _engine.load_library()
+    if getattr(lib.mifwt_swt2_fwd, "argtypes", None) is None:
+        _engine.register_entries(_SWT2_LAUNCHES)
+    return lib
+
+
+KID_SWT2, KID_ISWT2 = 34, 35  # kernel ids of the fused 2-D levels (``_engine.launch_count`` counts them under these ids)
 _rows = _engine._unit_last  # [B, N] with contiguous samples (row stride free)
 
 
@@ -334,4 +363,244 @@ def iswt(coeffs: Sequence[torch.Tensor], wavelet: Union[Wavelet, str], *, axis: 
             cur = _IswtLevel.apply(cur, det, rec_lo, rec_hi, dilation, 0.5, *((tap_t[2], tap_t[3]) if tap_t else (None, None)))
         else:
             cur = _level_inv(cur, det, rec_lo, rec_hi, dilation, 0.5)
+    return layout.unfold(cur)
+
+
+# ---- 2-D levels ---------------------------------------------------------------------------------------------------------------------------
+# A level takes FOUR filters (row_lo, row_hi along the last axis; col_lo, col_hi along the one before it): the transforms pass the
+# wavelet's pair twice, the tests pass four different ones.  Planes of a level buffer [B, 4, H, W]: cA, cH, cV, cD — cH is high-pass
+# along axis -2 and low-pass along axis -1, as wavedec2 names its bands.
+FORCE_COMPOSED = False  # True: every 2-D level takes the composed route (the fused kernels' cross-check and timing baseline)
+# (direction "fwd" / "inv", dtype, filter length) cells that stay on the composed route because the fused launch did not beat it
+# there (tools/swt2_bench.py, EXPERIMENTS.md "2-D stationary levels"): the project's rule for every fused kernel.
+COMPOSED2_CELLS: set = set()
+Taps4 = Tuple[Sequence[float], Sequence[float], Sequence[float], Sequence[float]]
+
+
+def _fused2(direction: str, dtype: torch.dtype, flen: int, b: int, h: int, w: int, dilation: int) -> bool:
+    """Does the fused 2-D launch serve this level?  (``mifwt_swt2_supported``: float32 / float64, even lengths up to 20.)"""
+    if FORCE_COMPOSED or dtype not in (torch.float32, torch.float64) or (direction, dtype, flen) in COMPOSED2_CELLS:
+        return False
+    return bool(_swt2_entries().mifwt_swt2_supported(_engine._DTYPE_IDS[dtype], flen, b, h, w, dilation))
+
+
+_merged: dict = {}
+
+
+def _merge_aliased(taps: Sequence[float], dilation: int, n: int) -> Tuple[float, ...]:
+    """Along an axis of ``n`` samples, taps m and m' read the same sample when ``D (m - m')`` is a multiple of n (extent 1: all of
+    them).  Their sum is taken HERE, in double, and put on the first tap of each such class (zeros on the others): the same level, but
+    a sum of many taps that cancels is no longer rounded tap by tap in the kernel's float32 (a 1 x 1 plane under 22 random taps came
+    out 1.1e-6 off, norm-wise, on both routes).  Filters whose taps all read different samples come back as they are."""
+    taps = tuple(taps)
+    flen = len(taps)
+    if n > dilation * (flen - 1):
+        return taps
+    key = (taps, dilation, n)
+    out = _merged.get(key)
+    if out is None:
+        classes: dict = {}
+        for m in range(flen):
+            classes.setdefault((dilation * m) % n, []).append(m)
+        merged = [0.0] * flen
+        for members in classes.values():
+            merged[members[0]] = math.fsum(taps[m] for m in members)
+        if len(_merged) > 512:
+            _merged.clear()
+        out = _merged[key] = tuple(merged)
+    return out
+
+
+def _merged4(taps: Taps4, dilation: int, h: int, w: int) -> Taps4:
+    return (_merge_aliased(taps[0], dilation, w), _merge_aliased(taps[1], dilation, w),
+            _merge_aliased(taps[2], dilation, h), _merge_aliased(taps[3], dilation, h))
+
+
+def _composed2_fwd(x: torch.Tensor, taps: Taps4, dilation: int, scale: float, tap_t=None) -> torch.Tensor:
+    """The level from 1-D level ops: along axis -1, then along axis -2 on a permuted copy.  Differentiable (data, and the taps when
+    ``tap_t`` = the four tap tensors is given) when grad mode is on."""
+    b, h, w = x.shape
+    tt = tap_t if tap_t is not None else (None,) * 4
+    diff = torch.is_grad_enabled() and (x.requires_grad or tap_t is not None)
+
+    def op(rows, lo, hi, s, lo_t, hi_t):
+        return _SwtLevel.apply(rows, lo, hi, dilation, s, lo_t, hi_t) if diff else _level_fwd(rows, lo, hi, dilation, s)
+
+    rows = op(x.reshape(b * h, w), taps[0], taps[1], 1.0, tt[0], tt[1]).reshape(b, h, 2, w)  # [B, H, row band, W]
+    cols = op(rows.permute(0, 2, 3, 1).reshape(b * 2 * w, h), taps[2], taps[3], scale, tt[2], tt[3])  # [B (row band) W, col band, H]
+    return cols.reshape(b, 2, w, 2, h).permute(0, 1, 3, 4, 2).reshape(b, 4, h, w)  # plane = 2 (row band) + (col band)
+
+
+def _composed2_inv(bands: Sequence[torch.Tensor], taps: Taps4, dilation: int, scale: float, tap_t=None) -> torch.Tensor:
+    """U = S_row(cA, cV), V = S_row(cH, cD), y = S_col(U, V) from the 1-D synthesis level op."""
+    ca, ch, cv, cd = bands
+    b, h, w = ca.shape
+    tt = tap_t if tap_t is not None else (None,) * 4
+    diff = torch.is_grad_enabled() and (any(t.requires_grad for t in bands) or tap_t is not None)
+
+    def op(a, d, lo, hi, s, lo_t, hi_t):
+        return _IswtLevel.apply(a, d, lo, hi, dilation, s, lo_t, hi_t) if diff else _level_inv(a, d, lo, hi, dilation, s)
+
+    lows = torch.stack((ca, ch)).reshape(2 * b * h, w)   # the operands the row filters' low-pass takes, for U and for V
+    highs = torch.stack((cv, cd)).reshape(2 * b * h, w)
+    uv = op(lows, highs, taps[0], taps[1], 1.0, tt[0], tt[1]).reshape(2, b, h, w).permute(0, 1, 3, 2).reshape(2, b * w, h)
+    y = op(uv[0], uv[1], taps[2], taps[3], scale, tt[2], tt[3])
+    return y.reshape(b, w, h).permute(0, 2, 1).contiguous()
+
+
+def _level2_fwd(x: torch.Tensor, taps: Taps4, dilation: int, scale: float, composed: bool = False) -> torch.Tensor:
+    """x [B, H, W] -> level buffer [B, 4, H, W] (planes cA, cH, cV, cD): the fused launch where it exists, else (or with
+    ``composed``) the composed route.  No autograd."""
+    _engine._require_gpu(x)
+    b, h, w = x.shape
+    flen = len(taps[0])
+    taps = _merged4(taps, dilation, h, w)
+    if composed or not _fused2("fwd", x.dtype, flen, b, h, w, dilation):
+        with torch.no_grad():
+            return _composed2_fwd(x.detach(), taps, dilation, scale)
+    x = _rows(x)
+    buf = torch.empty((b, 4, h, w), dtype=x.dtype, device=x.device)
+    if buf.numel() == 0:
+        return buf
+    plane = h * w * buf.element_size()
+    _engine._enqueue(x, _swt2_entries().mifwt_swt2_fwd, _engine._DTYPE_IDS[x.dtype], flen, b, h, w, dilation, x.data_ptr(),
+                     x.stride(0), x.stride(1), _vp4(*[buf.data_ptr() + q * plane for q in range(4)]), _i64x4(*[4 * h * w] * 4),
+                     _i64x4(*[w] * 4), *[_engine._taps_array(t) for t in taps], scale)
+    return buf
+
+
+def _level2_inv(bands: Sequence[torch.Tensor], taps: Taps4, dilation: int, scale: float, composed: bool = False) -> torch.Tensor:
+    """(cA, cH, cV, cD), each [B, H, W] with any image / row strides -> y [B, H, W].  No autograd."""
+    _engine._require_gpu(bands[0])
+    b, h, w = bands[0].shape
+    flen = len(taps[0])
+    taps = _merged4(taps, dilation, h, w)
+    if composed or not _fused2("inv", bands[0].dtype, flen, b, h, w, dilation):
+        with torch.no_grad():
+            return _composed2_inv([t.detach() for t in bands], taps, dilation, scale)
+    bands = [_rows(t) for t in bands]
+    y = torch.empty((b, h, w), dtype=bands[0].dtype, device=bands[0].device)
+    if y.numel() == 0:
+        return y
+    _engine._enqueue(y, _swt2_entries().mifwt_swt2_inv, _engine._DTYPE_IDS[y.dtype], flen, b, h, w, dilation,
+                     _vp4(*[t.data_ptr() for t in bands]), _i64x4(*[t.stride(0) for t in bands]), _i64x4(*[t.stride(1) for t in bands]),
+                     y.data_ptr(), h * w, w, *[_engine._taps_array(t) for t in taps], scale)
+    return y
+
+
+def _rev4(taps: Taps4) -> Taps4:
+    return tuple(t[::-1] for t in taps)
+
+
+class _Swt2Level(torch.autograd.Function):
+    """One 2-D analysis level with host taps and a free scale.  Its transpose is the synthesis level with all four filters reversed and
+    the same scale (and vice versa), so each Function's backward is the other Function: data gradients of any order."""
+
+    @staticmethod
+    def forward(ctx, x, taps, dilation, scale):
+        ctx.meta = (taps, dilation, scale)
+        return _level2_fwd(x, taps, dilation, scale)
+
+    @staticmethod
+    def backward(ctx, g_buf):
+        taps, dilation, scale = ctx.meta
+        return _Iswt2Level.apply(g_buf[:, 0], g_buf[:, 1], g_buf[:, 2], g_buf[:, 3], _rev4(taps), dilation, scale), None, None, None
+
+
+class _Iswt2Level(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ca, ch, cv, cd, taps, dilation, scale):
+        ctx.meta = (taps, dilation, scale)
+        return _level2_inv((ca, ch, cv, cd), taps, dilation, scale)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        taps, dilation, scale = ctx.meta
+        g = _Swt2Level.apply(g_y, _rev4(taps), dilation, scale)
+        return g[:, 0], g[:, 1], g[:, 2], g[:, 3], None, None, None
+
+
+def _check_dtype2(t: torch.Tensor) -> None:
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"Input dtype {t.dtype} not supported")
+
+
+def swt2(data: torch.Tensor, wavelet: Union[Wavelet, str], level: Optional[int] = None, *,
+         axes: Tuple[int, int] = (-2, -1)) -> WaveletCoeff2d:
+    """Multi-level 2-D stationary transform over ``axes``.  Returns ``[cA_n, WaveletDetailTuple2d(cH_n, cV_n, cD_n), ...,
+    WaveletDetailTuple2d(cH_1, cV_1, cD_1)]``, every tensor of the input's shape: the container of ``wavedec2``, with its band names
+    (``cH`` high-pass along ``axes[0]`` and low-pass along ``axes[1]``, ``cV`` the other way round, ``cD`` high-pass along both), and
+    equal to ``pywt.swt2(..., trim_approx=True, norm=False)``.
+
+    A level is the level of :func:`swt` (periodic, dilation ``2^level index``, scale 1) along both axes.  ``level=None`` means
+    ``min(swt_max_level(H), swt_max_level(W))`` — odd extents give ``[data]``; as in :func:`swt` no level is refused, the periodic index
+    map wraps as often as needed.  Only float32 and float64 are accepted: float16 raises ``ValueError("Input dtype ... not
+    supported")`` even inside ``half_storage()`` (the fused kernels have no float16 form).  Differentiable w.r.t. the data to any
+    order; a learnable (tensor-valued) filter bank runs on the composed route and has tap gradients up to second order."""
+    axes = _fwt._ensure_axes(axes, 2)
+    layout = _fwt._Layout(data, 2, axes)
+    _check_dtype2(data)
+    x = layout.fold(data)
+    dec_lo, dec_hi, _, _ = host_taps(wavelet)
+    tap_t = _fwt._tap_tensors(wavelet)
+    if level is None:
+        level = min(swt_max_level(x.shape[-2]), swt_max_level(x.shape[-1]))
+    taps = (tuple(dec_lo), tuple(dec_hi), tuple(dec_lo), tuple(dec_hi))
+    out: list = []
+    cur = x
+    for lvl in range(level):
+        _engine._require_gpu(cur)
+        if tap_t is not None:
+            buf = _composed2_fwd(cur, taps, 2 ** lvl, 1.0, (tap_t[0], tap_t[1], tap_t[0], tap_t[1]))
+        elif torch.is_grad_enabled() and cur.requires_grad:
+            buf = _Swt2Level.apply(cur, taps, 2 ** lvl, 1.0)
+        else:
+            buf = _level2_fwd(cur, taps, 2 ** lvl, 1.0)
+        out.append(WaveletDetailTuple2d(*(layout.unfold(buf[:, q]) for q in (1, 2, 3))))
+        cur = buf[:, 0]
+    out.append(layout.unfold(cur))
+    out.reverse()
+    return out
+
+
+def iswt2(coeffs: WaveletCoeff2d, wavelet: Union[Wavelet, str], *, axes: Tuple[int, int] = (-2, -1)) -> torch.Tensor:
+    """Inverse of :func:`swt2` (``pywt.iswt2`` of coefficients with ``trim_approx=True, norm=False``).  Per level ``U = S(cA, cV)`` and
+    ``V = S(cH, cD)`` along ``axes[1]``, ``y = S(U, V)`` along ``axes[0]``, with ``S`` the synthesis level of :func:`iswt` (scale 1/2
+    per axis): a linear map of ANY coefficient set, not only of images of ``swt2``.  float32 / float64 only, as :func:`swt2`."""
+    coeffs = list(coeffs)
+    if not coeffs or not isinstance(coeffs[0], torch.Tensor):
+        raise ValueError("First element of coeffs must be the approximation coefficient tensor.")
+    axes = _fwt._ensure_axes(axes, 2)
+    layout = _fwt._Layout(coeffs[0], 2, axes)
+    flat = [coeffs[0]]
+    for c in coeffs[1:]:
+        if not isinstance(c, tuple) or len(c) != 3:
+            raise ValueError(f"Unexpected detail coefficient type: {type(c)}. Detail coefficients must be a 3-tuple of tensors as "
+                             "returned by swt2.")
+        for t in c:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"Unexpected input type {type(t)}")
+        flat.extend(c)
+    _fwt._check_same_device_dtype(flat)
+    _check_dtype2(coeffs[0])
+    _, _, rec_lo, rec_hi = host_taps(wavelet)
+    tap_t = _fwt._tap_tensors(wavelet)
+    taps = (tuple(rec_lo), tuple(rec_hi), tuple(rec_lo), tuple(rec_hi))
+    cur = layout.fold(coeffs[0])
+    details = [tuple(layout.fold(t) for t in c) for c in coeffs[1:]]
+    for pos, det in enumerate(details):
+        for t in det:
+            if t.shape != cur.shape:
+                raise ValueError(f"detail coefficients of shape {tuple(t.shape)} do not match the approximation of shape "
+                                 f"{tuple(cur.shape)} (folded to [batch, H, W])")
+    for pos, det in enumerate(details):
+        dilation = 2 ** (len(details) - pos - 1)
+        bands = (cur, *det)
+        _engine._require_gpu(cur)
+        if tap_t is not None:
+            cur = _composed2_inv(bands, taps, dilation, 0.25, (tap_t[2], tap_t[3], tap_t[2], tap_t[3]))
+        elif torch.is_grad_enabled() and any(t.requires_grad for t in bands):
+            cur = _Iswt2Level.apply(*bands, taps, dilation, 0.25)
+        else:
+            cur = _level2_inv(bands, taps, dilation, 0.25)
     return layout.unfold(cur)
