@@ -72,16 +72,14 @@ def _analysis_tap_grads(x, g_buf, dec_lo, dec_hi, mode_id):
     for a in range(nd):
         if nd == 1:
             parts = [x]  # [B, N]
-            part_axis = 0
         else:
             xa = x.movedim(1 + a, 1)  # [B, N_a, others..]
             flat = xa.reshape(-1, *xa.shape[2:])
             pb = eng.analysis(flat, dec_lo, dec_hi, mode_id)  # [B * N_a, 2^(nd-1), M_others..]
             pb = pb.reshape(xa.shape[0], xa.shape[1], *pb.shape[1:])  # [B, N_a, 2^(nd-1), M_others..]
             parts = [pb[:, :, r] for r in range(1 << (nd - 1))]  # each [B, N_a, M_others..]
-            part_axis = 0
         for r, z in enumerate(parts):
-            z2 = _rows_last(z, part_axis) if nd > 1 else z
+            z2 = _rows_last(z, 0) if nd > 1 else z
             for sigma, out in ((0, g_lo), (1, g_hi)):
                 band = _band_index(nd, a, sigma, r)
                 g2 = _rows_last(g_buf[:, band], a)
@@ -154,6 +152,15 @@ def _host_taps_of(t: torch.Tensor, device: Optional[torch.device] = None):
     return [float(v) for v in t.detach().double().cpu().reshape(-1).tolist()]
 
 
+def _tap_pair(needed: bool, corr, lo_t: torch.Tensor, hi_t: torch.Tensor, *args):
+    """The tap gradients of a per-axis op's backward: ``corr.apply(*args)`` (float64 [L] each) cast like the tap tensors, or
+    ``(None, None)`` when neither is asked for."""
+    if not needed:
+        return None, None
+    t_lo, t_hi = corr.apply(*args)
+    return _like(t_lo, lo_t), _like(t_hi, hi_t)
+
+
 class _Axis1(torch.autograd.Function):
     """rows [R, N] -> [R, 2, M]: one analysis level along the last axis, taps as tensors."""
 
@@ -167,10 +174,7 @@ class _Axis1(torch.autograd.Function):
     def backward(ctx, g):
         x, lo_t, hi_t = ctx.saved_tensors
         g_x = _Axis1Adj.apply(g, lo_t, hi_t, ctx.mode_id, x.shape[1]) if ctx.needs_input_grad[0] else None
-        t_lo = t_hi = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            t_lo, t_hi = _Axis1Corr.apply(x, g, lo_t.numel(), ctx.mode_id)
-            t_lo, t_hi = _like(t_lo, lo_t), _like(t_hi, hi_t)
+        t_lo, t_hi = _tap_pair(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], _Axis1Corr, lo_t, hi_t, x, g, lo_t.numel(), ctx.mode_id)
         return g_x, t_lo, t_hi, None
 
 
@@ -187,10 +191,8 @@ class _Axis1Adj(torch.autograd.Function):
     def backward(ctx, gg):
         g, lo_t, hi_t = ctx.saved_tensors
         g_g = _Axis1.apply(gg, lo_t, hi_t, ctx.mode_id) if ctx.needs_input_grad[0] else None
-        t_lo = t_hi = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # <gg, A(h)^T g> = <A(h) gg, g>
-            t_lo, t_hi = _Axis1Corr.apply(gg, g, lo_t.numel(), ctx.mode_id)
-            t_lo, t_hi = _like(t_lo, lo_t), _like(t_hi, hi_t)
+        # <gg, A(h)^T g> = <A(h) gg, g>
+        t_lo, t_hi = _tap_pair(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], _Axis1Corr, lo_t, hi_t, gg, g, lo_t.numel(), ctx.mode_id)
         return g_g, t_lo, t_hi, None, None
 
 
@@ -231,10 +233,7 @@ class _Syn1(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gb = _Syn1Adj.apply(g_y, lo_t, hi_t, a.shape[1])
             g_a, g_d = gb[:, 0], gb[:, 1]
-        t_lo = t_hi = None
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            t_lo, t_hi = _Syn1Corr.apply(a, d, g_y, lo_t.numel())
-            t_lo, t_hi = _like(t_lo, lo_t), _like(t_hi, hi_t)
+        t_lo, t_hi = _tap_pair(ctx.needs_input_grad[2] or ctx.needs_input_grad[3], _Syn1Corr, lo_t, hi_t, a, d, g_y, lo_t.numel())
         return g_a, g_d, t_lo, t_hi, None
 
 
@@ -250,10 +249,8 @@ class _Syn1Adj(torch.autograd.Function):
     def backward(ctx, gg):
         g_y, lo_t, hi_t = ctx.saved_tensors
         g_gy = _Syn1.apply(gg[:, 0], gg[:, 1], lo_t, hi_t, g_y.shape[1]) if ctx.needs_input_grad[0] else None
-        t_lo = t_hi = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # <gg, S(r)^T g_y> = <S(r) gg, g_y>
-            t_lo, t_hi = _Syn1Corr.apply(gg[:, 0], gg[:, 1], g_y, lo_t.numel())
-            t_lo, t_hi = _like(t_lo, lo_t), _like(t_hi, hi_t)
+        # <gg, S(r)^T g_y> = <S(r) gg, g_y>
+        t_lo, t_hi = _tap_pair(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], _Syn1Corr, lo_t, hi_t, gg[:, 0], gg[:, 1], g_y, lo_t.numel())
         return g_gy, t_lo, t_hi, None
 
 
@@ -459,6 +456,17 @@ class _AnalysisAdjointBands(torch.autograd.Function):
         return (None, None, None, None) + tuple(buf[:, s] for s in range(ndet + 1))
 
 
+def _chained_analysis_adjoint(meta, g, g_bands):
+    """Backward of a multi-level analysis launch, level by level from the coarsest: ``g`` = the gradient of the last level's
+    approximation, ``g_bands`` = those of the detail bands (as many per level as the launch has), finest level first; ``meta`` = (input
+    shape per level, dec taps, mode).  Each step is a differentiable op in turn (gradients of any order)."""
+    shapes, dec_lo, dec_hi, mode_id = meta
+    ndet = len(g_bands) // len(shapes)
+    for lvl in range(len(shapes) - 1, -1, -1):
+        g = _AnalysisAdjointBands.apply(shapes[lvl], dec_lo, dec_hi, mode_id, g, *g_bands[ndet * lvl : ndet * lvl + ndet])
+    return g
+
+
 class _AnalysisPyramid(torch.autograd.Function):
     """Several 2-D analysis levels in ONE launch as a differentiable op w.r.t. the data (C ABI ``mifwt_dwt2_fwd_pyramid``: the streaming
     three-level kernel / the small-plane kernel; src/ptwt/conv_transform_2.py:142-149 per trip): the forward of a call that asks for
@@ -490,10 +498,7 @@ class _AnalysisPyramid(torch.autograd.Function):
                                                  list(shapes[0]))
             if g is not None:
                 return g, None, None, None, None
-        g = g_approx
-        for lvl in range(len(shapes) - 1, -1, -1):
-            g = _AnalysisAdjointBands.apply(shapes[lvl], dec_lo, dec_hi, mode_id, g, *g_bands[3 * lvl : 3 * lvl + 3])
-        return g, None, None, None, None
+        return _chained_analysis_adjoint(ctx.meta, g_approx, g_bands), None, None, None, None
 
 
 class _FusedRouteUnavailable(Exception):
@@ -520,11 +525,49 @@ class _AnalysisTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_approx, *g_details):
-        shapes, dec_lo, dec_hi, mode_id = ctx.meta
-        g = g_approx
-        for lvl in range(len(shapes) - 1, -1, -1):
-            g = _AnalysisAdjointBands.apply(shapes[lvl], dec_lo, dec_hi, mode_id, g, g_details[lvl])
-        return g, None, None, None, None
+        return _chained_analysis_adjoint(ctx.meta, g_approx, g_details), None, None, None, None
+
+
+def _chained_synthesis_adjoint(meta, g_y, ndet: int, fused_launch):
+    """Backward of a multi-level reconstruction w.r.t. its coefficients, level by level from the finest: ``meta`` = (rec taps, shape of
+    the coefficients per level, coarsest first), ``ndet`` detail bands per level.  Returns (gradient of the coarsest approximation,
+    [gradients of the detail bands, coarsest level first]).  Each step is :class:`_SynthesisAdjointLevel`, a differentiable op in turn.
+
+    No graph of the backward wanted and host taps: the adjoint of a synthesis level is a zero-mode analysis level with the rec taps
+    reversed, and a trimmed output sample is a zero the zero extension supplies anyway — so the adjoint of several levels is ONE
+    multi-level analysis launch where the library serves it.  ``fused_launch(g, lo, hi, n)`` is that launch over up to ``n`` levels:
+    level buffers like those of ``analysis_pyramid`` / ``analysis_tail``, or None (None in its place: there is no such launch)."""
+    rec_lo, rec_hi, coef_shapes = meta
+    flen = len(rec_lo)
+    grads: list = []
+    g = g_y
+    todo = list(reversed(coef_shapes))  # finest level first
+    fused = fused_launch is not None and not torch.is_grad_enabled() and not _engine._is_dev(rec_lo)
+    while todo:
+        bufs = None
+        if fused and len(todo) >= 2:
+            # what a zero-mode analysis of g yields level by level (floor((n + L - 1) / 2) per axis) against the coefficient shapes the
+            # forward took: decided on the host BEFORE anything is launched — a chain with a crop the adjoint launch cannot express (a
+            # separable crop of more than one sample) goes level by level from here on instead of launching, discarding and retrying
+            ns, ok = [int(v) for v in g.shape[1:]], 0
+            for shp in todo:
+                ns = [(n + flen - 1) // 2 for n in ns]
+                if tuple(ns) != tuple(shp):
+                    break
+                ok += 1
+            if ok < 2:
+                fused = False
+            else:
+                bufs = fused_launch(g if g.stride(-1) == 1 else g.contiguous(), list(rec_lo)[::-1], list(rec_hi)[::-1], ok)
+                if bufs is not None and (len(bufs) < 2 or any(tuple(b.shape[2:]) != tuple(shp) for b, shp in zip(bufs, todo))):
+                    bufs, fused = None, False
+        if bufs is None:
+            bufs = [_SynthesisAdjointLevel.apply(g, todo[0], rec_lo, rec_hi)]
+        for b in bufs:  # (the detail bands are the last planes of a level buffer, the approximation of the last one its first)
+            grads = list(b.unbind(1)[-ndet:]) + grads
+        g = bufs[-1][:, 0]
+        todo = todo[len(bufs):]
+    return g, grads
 
 
 class _SynthesisChain1d(torch.autograd.Function):
@@ -539,43 +582,8 @@ class _SynthesisChain1d(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_y):
-        rec_lo, rec_hi, coef_shapes = ctx.meta
-        grads: list = []
-        g = g_y
-        todo = list(reversed(coef_shapes))  # finest level first
-        # no graph of the backward wanted: the adjoint of the chain is a zero-mode multi-level ANALYSIS with the rec taps reversed (a
-        # trimmed output sample is a zero of the zero extension) — the 1-D multi-level launches (kernels 17 / 14), see _SynthesisPyramid
-        fused = not torch.is_grad_enabled() and not _engine._is_dev(rec_lo) and g_y.dim() == 2
-        zero = _engine.MODE_IDS["zero"]
-        flen = len(rec_lo)
-        while todo:
-            bufs = None
-            if fused and len(todo) >= 2:
-                # what a zero-mode analysis of g yields level by level (floor((n + L - 1) / 2)) against the coefficient shapes the forward
-                # took: decided on the host BEFORE anything is launched — a chain with a crop the adjoint launch cannot express (a
-                # separable crop of more than one sample) goes level by level from here on instead of launching, discarding and retrying
-                n, ok = int(g.shape[-1]), 0
-                for shp in todo:
-                    n = (n + flen - 1) // 2
-                    if (n,) != tuple(shp):
-                        break
-                    ok += 1
-                if ok < 2:
-                    fused = False
-                else:
-                    bufs = _engine.ENGINE.analysis_tail(g if g.stride(-1) == 1 else g.contiguous(), list(rec_lo)[::-1], list(rec_hi)[::-1], zero, ok)
-                    if bufs is not None and (len(bufs) < 2 or any(tuple(b.shape[2:]) != tuple(shp) for b, shp in zip(bufs, todo))):
-                        bufs, fused = None, False
-            if bufs is None:
-                gb = _SynthesisAdjointLevel.apply(g, todo[0], rec_lo, rec_hi)
-                grads.insert(0, gb[:, 1])
-                g = gb[:, 0]
-                todo = todo[1:]
-            else:
-                for b in bufs:
-                    grads.insert(0, b[:, -1])
-                g = bufs[-1][:, 0]
-                todo = todo[len(bufs):]
+        zero = _engine.MODE_IDS["zero"]  # (kernels 17 / 14)
+        g, grads = _chained_synthesis_adjoint(ctx.meta, g_y, 1, lambda g, lo, hi, n: _engine.ENGINE.analysis_tail(g, lo, hi, zero, n))
         return (None, None, None, g, *grads)
 
 
@@ -654,45 +662,20 @@ class _SynthesisPyramid(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_y):
-        rec_lo, rec_hi, coef_shapes = ctx.meta
-        grads: list = []
-        g = g_y
-        todo = list(reversed(coef_shapes))  # finest level first: its adjoint yields the gradient of its four bands
-        # No graph of the backward wanted: the adjoint of a synthesis level is a zero-mode analysis level with the rec taps reversed, and a
-        # trimmed output row / column is a zero the zero extension supplies anyway — so the adjoint of the whole reconstruction is ONE
-        # multi-level analysis launch (kernels 16 / 20) where the library serves it (the mirror of _AnalysisPyramid.backward).
-        fused = not torch.is_grad_enabled() and not _engine._is_dev(rec_lo) and g_y.dim() == 3 and g_y.dtype == torch.float32
-        zero = _engine.MODE_IDS["zero"]
-        while todo:
-            bufs = None
-            if fused and len(todo) >= 2:
-                gin = g if g.stride(-1) == 1 else g.contiguous()
-                # the zero-mode analysis extents (floor((n + L - 1) / 2) per axis and level) against the coefficient shapes of the forward,
-                # on the host, before anything is launched: a crop the adjoint launch cannot express sends the rest level by level
-                ns, ok = [int(v) for v in gin.shape[1:]], 0
-                for shp in todo:
-                    ns = [(n + len(rec_lo) - 1) // 2 for n in ns]
-                    if tuple(ns) != tuple(shp):
-                        break
-                    ok += 1
-                k = _engine.ENGINE.pyramid_levels(gin, len(rec_lo), zero, ok) if ok >= 2 else 0  # (a query: nothing is launched)
-                if ok < 2:
-                    fused = False
-                if k >= 2:
-                    bufs = _engine.ENGINE.analysis_pyramid(gin, list(rec_lo)[::-1], list(rec_hi)[::-1], zero, k)
-                if bufs is not None and (len(bufs) < 2 or any(tuple(b.shape[2:]) != tuple(shp) for b, shp in zip(bufs, todo))):
-                    bufs, fused = None, False
-            if bufs is None:
-                gb = _SynthesisAdjointLevel.apply(g, todo[0], rec_lo, rec_hi)
-                grads = [gb[:, 1], gb[:, 2], gb[:, 3]] + grads
-                g = gb[:, 0]  # = the gradient of the coarser level's (trimmed) output
-                todo = todo[1:]
-            else:
-                for b in bufs:
-                    grads = list(b.unbind(1)[-3:]) + grads
-                g = bufs[-1][:, 0]
-                todo = todo[len(bufs):]
+        zero, eng = _engine.MODE_IDS["zero"], _engine.ENGINE
+
+        def launch(g, lo, hi, n):  # (kernels 16 / 20, the mirror of _AnalysisPyramid.backward; the query launches nothing)
+            k = eng.pyramid_levels(g, len(lo), zero, n)
+            return eng.analysis_pyramid(g, lo, hi, zero, k) if k >= 2 else None
+
+        g, grads = _chained_synthesis_adjoint(ctx.meta, g_y, 3, launch if g_y.dtype == torch.float32 else None)
         return (None, None, None, None, None, g, *grads)
+
+
+def _graph_taps(tap_t, first: int):
+    """What ties a level op to a learnable filter bank: its tap TENSORS ``first`` and ``first + 1`` of :func:`_tap_tensors` (0: the
+    dec pair, 2: the rec pair), or ``(None, None)``."""
+    return (None, None) if tap_t is None else (tap_t[first], tap_t[first + 1])
 
 
 def _tap_tensors(wavelet):
@@ -818,9 +801,21 @@ def _check_pad(extents: Sequence[int], flen: int, mode: str) -> None:
 
 # ------------------------------------------------------------------------------------------ analysis
 # geometry of a graph-free decomposition -> the launches it took ((0, levels asked of the multi-level launch) / (1, 0) level pair /
-# (2, levels) 1-D tail / (3, 0) one level); idempotent values, single dict operations (see the synthesis memos below)
+# (2, levels) 1-D tail / (3, 0) one level); idempotent values, single dict operations (see the synthesis memo below)
 _route_memo: dict = {}
 _engine._routing_caches.append(_route_memo)
+
+
+def _check_pad_levels(extents: Sequence[int], flen: int, mode, level: int) -> None:
+    """The pad check of every trip of the reference's level loop (:func:`_check_pad`), walked ONCE over all ``level`` levels of a
+    geometry: raises the reference's error for the first level that fails.  Every trip and every fused route relies on it."""
+    mode = "reflect" if mode is None else mode
+    if mode not in ("reflect", "periodic"):
+        return
+    ns = list(extents)
+    for _ in range(level):
+        _check_pad(ns, flen, mode)
+        ns = [(n + flen - 1) // 2 for n in ns]
 
 
 def analysis(data: torch.Tensor, wavelet, mode, level: Optional[int], axes: AxisHint, ndim: int):
@@ -838,132 +833,97 @@ def analysis(data: torch.Tensor, wavelet, mode, level: Optional[int], axes: Axis
     flen = len(dec_lo)
     if level is None:
         level = dwtn_max_level(x.shape[1:], flen)
-    bufs: List[torch.Tensor] = []
-    cur = x
-    done = 0
+    eng = _engine.ENGINE
+    # the call builds a graph: every level runs as an autograd op.  (A learnable filter bank — `tap_t`, which implies a graph — takes
+    # the per-level ops, which also produce tap gradients; device-resident taps take the per-level generic route.)
+    differentiable = torch.is_grad_enabled() and (x.requires_grad or tap_t is not None)
+    fusable = not on_device and tap_t is None
     # Calls that need no graph (inference: the common case, and every timed loop) REPLAY the launches their geometry took last time:
-    # which levels fuse is a function of the geometry and the routing options alone, and the pad checks below raise by geometry alone —
-    # a geometry is memoised only after it passed them.  (32 x 1000^2 db5 periodic level 5, five launches: 79 -> ~60 us of host time a
+    # which levels fuse is a function of the geometry and the routing options alone, and the pad checks raise by geometry alone — a
+    # geometry is memoised only after it passed them.  (32 x 1000^2 db5 periodic level 5, five launches: 79 -> ~60 us of host time a
     # call, which is what that call costs once the GPU needs less: tools/host_profile_ref.py)
-    rkey = None
-    if not on_device and not (torch.is_grad_enabled() and (x.requires_grad or tap_t is not None)):
+    rkey = plan = None
+    if not (on_device or differentiable):
         mode_id = _mode_id(mode)
-        eng = _engine.ENGINE
         rkey = (ndim, x.shape, x.stride(), x.dtype, x.device, flen, mode_id, level, id(eng), _engine.MAX_PYRAMID_LEVELS, _engine.ROW_ALIGN,
                 _engine.PYRAMID_ROW_ALIGN)
-        steps = _route_memo.get(rkey)
-        if steps is not None:
-            for kind, arg in steps:
-                if kind == 0:
-                    got = eng.analysis_pyramid(cur, dec_lo, dec_hi, mode_id, arg)
-                elif kind == 1:
-                    got = eng.analysis_pair(cur, dec_lo, dec_hi, mode_id)
-                elif kind == 2:
-                    got = eng.analysis_tail(cur, dec_lo, dec_hi, mode_id, arg)
-                else:
-                    got = (eng.analysis(cur, dec_lo, dec_hi, mode_id),)
-                if got is None:  # (cannot happen while the memo is cleared with the plans; never guess: take the long way)
-                    break
-                bufs.extend(got)
-                cur = got[-1][:, 0]
-            else:
-                bufs.reverse()
-                return layout, cur, bufs
-            _route_memo.pop(rkey, None)
-            bufs, cur = [], x
-    steps = []
-    while done < level:
+        plan = _route_memo.get(rkey)
+    elif level > 0:  # (only a trip of the level loop looks at the mode)
         mode_id = _mode_id(mode)
-        _check_pad(cur.shape[1:], flen, "reflect" if mode is None else mode)
-        differentiable = torch.is_grad_enabled() and (cur.requires_grad or tap_t is not None)
-        if ndim == 2 and not on_device and (not differentiable or tap_t is None):
-            # several levels per launch (three of a big plane, the whole pyramid of a small one), the approximations between them kept
-            # on chip (mifwt_dwt2_fwd_pyramid); the pad
-            # checks of the fused trips are the reference's own and run before anything is launched
-            want = min(_engine.MAX_PYRAMID_LEVELS, level - done)
-            ns = list(cur.shape[1:])
-            for _l in range(want):
-                _check_pad(ns, flen, "reflect" if mode is None else mode)
-                ns = [(n + flen - 1) // 2 for n in ns]
-            if differentiable:
-                # gradients w.r.t. the data only (a learnable filter bank takes the per-level ops, which also produce tap gradients):
-                # the same launch as a differentiable op
-                if _engine.ENGINE.pyramid_levels(cur, flen, mode_id, want) > 0:
-                    bands = _AnalysisPyramid.apply(cur, dec_lo, dec_hi, mode_id, want)
-                    cur = bands[0]
-                    nfused = (len(bands) - 1) // 3
-                    bufs.extend(bands[1 + 3 * l : 4 + 3 * l] for l in range(nfused))  # (a level as its three bands: pack_2d / pack_dict take either form)
-                    done += nfused
-                    continue
-            else:
-                pyr = _engine.ENGINE.analysis_pyramid(cur, dec_lo, dec_hi, mode_id, want)
-                if pyr is not None:
-                    steps.append((0, want))
-                    bufs.extend(pyr)
-                    cur = pyr[-1][:, 0]
-                    done += len(pyr)
-                    continue
-        if ndim == 2 and level - done >= 2 and not differentiable and not on_device:
-            # two levels per launch, the approximation between them kept on chip (mifwt_dwt2_fwd_pair); the second
-            # level's reflect / periodic pad check is the reference's own (it would raise inside the next trip)
-            n1 = [(n + flen - 1) // 2 for n in cur.shape[1:]]
-            _check_pad(n1, flen, "reflect" if mode is None else mode)
-            pair = _engine.ENGINE.analysis_pair(cur, dec_lo, dec_hi, mode_id)
-            if pair is not None:
-                steps.append((1, 0))
-                bufs.extend(pair)
-                cur = pair[1][:, 0]
-                done += 2
-                continue
-        if ndim == 1 and level - done >= 2 and not on_device and (not differentiable or tap_t is None):
-            # the deep levels of a 1-D pyramid in one launch (mifwt_dwt1_fwd_tail) once a row fits into LDS, several levels of
-            # longer rows per launch before that (mifwt_dwt1_fwd_long); the pad checks of the fused trips are the reference's
-            # own and run before anything is launched
-            n = cur.shape[1]
-            for _l in range(level - done):
-                _check_pad([n], flen, "reflect" if mode is None else mode)
-                n = (n + flen - 1) // 2
-            if differentiable:  # (gradients w.r.t. the data only: the same launches as a differentiable op)
+    if plan is None:
+        _check_pad_levels(x.shape[1:], flen, mode, level)
+    bufs: list = []  # coarsest level first
+    steps: list = []
+    cur, done, taken = x, 0, 0
+    while done < level:
+        if plan is not None:
+            cands = (plan[taken],)
+            taken += 1
+        else:  # the routes in the order they are tried; the last one serves everything
+            left = level - done
+            cands = []
+            if ndim == 2 and fusable:
+                cands.append((0, min(_engine.MAX_PYRAMID_LEVELS, left)))
+                if left >= 2 and not differentiable:
+                    cands.append((1, 0))
+            if ndim == 1 and fusable and left >= 2:
+                cands.append((2, left))
+            cands.append((3, 0))
+        for kind, arg in cands:
+            # (a differentiable multi-level op hands out the next approximation, `nxt`, and each level as a tuple of its detail bands: the
+            # pack_* functions take either form)
+            nxt = None
+            if kind == 0 and differentiable:
+                # several 2-D levels per launch as ONE differentiable op where the library serves them (a query: nothing is launched)
+                got = None
+                if eng.pyramid_levels(cur, flen, mode_id, arg) > 0:
+                    nxt, *bands = _AnalysisPyramid.apply(cur, dec_lo, dec_hi, mode_id, arg)
+                    got = [tuple(bands[i : i + 3]) for i in range(0, len(bands), 3)]
+            elif kind == 0:
+                # several levels per launch (three of a big plane, the whole pyramid of a small one), the approximations between them kept
+                # on chip (mifwt_dwt2_fwd_pyramid); may fuse fewer levels than asked
+                got = eng.analysis_pyramid(cur, dec_lo, dec_hi, mode_id, arg)
+            elif kind == 1:
+                # two levels per launch, the approximation between them kept on chip (mifwt_dwt2_fwd_pair)
+                got = eng.analysis_pair(cur, dec_lo, dec_hi, mode_id)
+            elif kind == 2 and differentiable:
                 try:
-                    bands = _AnalysisTail.apply(cur, dec_lo, dec_hi, mode_id, level - done)
+                    nxt, *bands = _AnalysisTail.apply(cur, dec_lo, dec_hi, mode_id, arg)
+                    got = [(d,) for d in bands]
                 except _FusedRouteUnavailable:
-                    bands = None
-                if bands is not None:
-                    cur = bands[0]
-                    bufs.extend((d,) for d in bands[1:])  # (a level as its detail row: pack_1d takes either form)
-                    done += len(bands) - 1
-                    continue
+                    got = None
+            elif kind == 2:
+                # the deep levels of a 1-D pyramid in one launch (mifwt_dwt1_fwd_tail) once a row fits into LDS, several levels of
+                # longer rows per launch before that (mifwt_dwt1_fwd_long)
+                got = eng.analysis_tail(cur, dec_lo, dec_hi, mode_id, arg)
+            elif differentiable:
+                got = (_AnalysisLevel.apply(cur, dec_lo, dec_hi, mode_id, *_graph_taps(tap_t, 0)),)
             else:
-                tail = _engine.ENGINE.analysis_tail(cur, dec_lo, dec_hi, mode_id, level - done)
-                if tail is not None:
-                    steps.append((2, level - done))
-                    bufs.extend(tail)
-                    cur = tail[-1][:, 0]
-                    done += len(tail)
-                    continue
-        done += 1
-        if differentiable:
-            buf = _AnalysisLevel.apply(cur, dec_lo, dec_hi, mode_id, *((tap_t[0], tap_t[1]) if tap_t else (None, None)))
-        else:
-            steps.append((3, 0))
-            buf = _engine.ENGINE.analysis(cur, dec_lo, dec_hi, mode_id)
-        bufs.append(buf)
-        cur = buf[:, 0]
-    if rkey is not None:
+                got = (eng.analysis(cur, dec_lo, dec_hi, mode_id),)
+            if got is not None:
+                break
+        else:  # a replayed step refused (cannot happen while the memo is cleared with the plans; never guess: take the long way)
+            _route_memo.pop(rkey, None)
+            return analysis(data, wavelet, mode, level, axes, ndim)
+        if plan is None:
+            steps.append((kind, arg))
+        bufs[:0] = got[::-1]
+        done += len(got)
+        cur = got[-1][:, 0] if nxt is None else nxt
+    if rkey is not None and plan is None:
         if len(_route_memo) > 512:
             _route_memo.clear()
         _route_memo[rkey] = tuple(steps)
-    bufs.reverse()
     return layout, cur, bufs
 
 
 # ------------------------------------------------------------------------------------------ synthesis
-# (both memos hold idempotent values and are only touched through single dict operations — get / item assignment / clear — each atomic
-# under the GIL; a thread that loses a race recomputes the same entry)
-_tail_memo: dict = {}  # geometry of a 2-D reconstruction -> (levels the streaming launch takes, final extents, its plan)
-_small_memo: dict = {}  # ... of a small plane -> (final extents, plan of the one-launch reconstruction)
-_engine._routing_caches.append(_tail_memo)
-_engine._routing_caches.append(_small_memo)
+# geometry of a reconstruction that passed the reference's checks -> (output extents per level, the level at which ONE launch takes over
+# the rest of a 2-D reconstruction — the number of levels: no such launch —, the plan of that launch).  Idempotent values, only touched
+# through single dict operations — get / item assignment / clear — each atomic under the GIL; a thread that loses a race recomputes the
+# same entry.
+_rec_memo: dict = {}
+_engine._routing_caches.append(_rec_memo)
 
 
 def _adjust_trim(res_size: int, next_size: int) -> int:
@@ -986,6 +946,60 @@ def _check_same_device_dtype(tensors: Sequence[torch.Tensor]) -> None:
             raise ValueError("coefficients must have the same dtype")
 
 
+def _walk_synthesis(shape: Tuple[int, ...], folded, flen: int, ndim: int, separable: bool):
+    """The checks of every trip of the reference's level loop (shapes, trims), walked ONCE over a reconstruction: ``shape`` = the folded
+    approximation's.  Returns the output extents of the levels that pass, coarsest first, and the exception the reference raises at the
+    level after them (None: every level passes)."""
+    exts: list = []
+    try:
+        for pos, det in enumerate(folded):
+            trims = [0] * ndim
+            if separable:
+                # the separable reference crops the running approximation to the detail shape
+                # (src/ptwt/separable_conv_transform.py:94-97) and never trims the synthesis output
+                shape = tuple(min(c, s_) for c, s_ in zip(shape, det[0].shape))
+            elif pos + 1 < len(folded):
+                nxt = folded[pos + 1][0].shape
+                trims = [_adjust_trim(2 * shape[1 + a] - flen + 2, nxt[1 + a]) for a in range(ndim)]
+            for t in det:
+                if tuple(t.shape) != tuple(shape):
+                    if ndim == 1:  # torch.stack in the reference (src/ptwt/conv_transform.py:186)
+                        raise RuntimeError("stack expects each tensor to be equal size")
+                    raise ValueError("All coefficients on each level must have the same shape")
+            out_ext = [2 * shape[1 + a] - flen + 2 - trims[a] for a in range(ndim)]
+            if min(out_ext) < 1:
+                raise ValueError("coefficients too short for this wavelet")
+            exts.append(out_ext)
+            shape = (shape[0], *out_ext)
+    except (ValueError, RuntimeError, AssertionError) as err:
+        return exts, err
+    return exts, None
+
+
+def _pyramid_route(cur: torch.Tensor, folded, exts, flen: int, separable: bool):
+    """Which levels of a 2-D float32 reconstruction go in ONE launch, the running approximation kept on chip (mifwt_dwt2_inv_pyramid):
+    ``(first level of that launch, its plan)`` — every level of a small plane, the FINEST up to three of a big one (that is where the
+    bytes are; what is coarser goes first, level by level) — or ``(number of levels, None)``.  Geometry only; ``exts`` from the walk."""
+    eng, nlev = _engine.ENGINE, len(folded)
+    if cur.dtype != torch.float32:
+        return nlev, None
+    if folded[-1][0].shape[-1] * folded[-1][0].shape[-2] <= 10240:  # (the finest level's four coefficient planes must fit into LDS)
+        pl = eng.synthesis_pyramid_plan(cur, folded, flen, exts[-1])
+        return (0, pl) if pl is not None and pl[3] else (nlev, None)
+    for first in range(max(nlev - 3, 0), nlev):
+        if first == 0:
+            a0 = cur[tuple(slice(0, s_) for s_ in folded[0][0].shape)] if separable else cur
+        else:  # the approximation the coarser levels will hand over: dense, cropped to the level's band extents
+            ext = (cur.shape[0], *exts[first - 1])
+            if separable:
+                ext = tuple(min(c, s_) for c, s_ in zip(ext, folded[first][0].shape))
+            a0 = torch.empty(ext, dtype=cur.dtype, device="meta")
+        pl = eng.synthesis_pyramid_plan(a0, folded[first:], flen, exts[-1])
+        if pl is not None and pl[3] == 2:
+            return first, pl
+    return nlev, None
+
+
 def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, axes: AxisHint, ndim: int,
               separable: bool) -> torch.Tensor:
     """Multi-level synthesis.  ``levels``: per level (coarsest first) the 2^n-1 detail tensors in band order."""
@@ -1006,184 +1020,109 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
     flen = len(rec_lo)
     cur = layout.fold(approx)
     folded = [[layout.fold(t) for t in lvl] for lvl in levels]
-    def level_out_extent(cur_shape, pos):
-        """Checks of one trip of the reference's level loop (shapes, trims) -> output extents of that level."""
-        det = folded[pos]
-        if separable:
-            # the separable reference crops the running approximation to the detail shape
-            # (src/ptwt/separable_conv_transform.py:94-97) and never trims the synthesis output
-            cur_shape = tuple(min(c, s_) for c, s_ in zip(cur_shape, det[0].shape))
-            trims = [0] * ndim
-        else:
-            trims = [0] * ndim
-            if pos + 1 < len(folded):
-                nxt = folded[pos + 1][0].shape
-                trims = [_adjust_trim(2 * cur_shape[1 + a] - flen + 2, nxt[1 + a]) for a in range(ndim)]
-        for t in det:
-            if tuple(t.shape) != tuple(cur_shape):
-                if ndim == 1:  # torch.stack in the reference (src/ptwt/conv_transform.py:186)
-                    raise RuntimeError("stack expects each tensor to be equal size")
-                raise ValueError("All coefficients on each level must have the same shape")
-        out_ext = [2 * cur_shape[1 + a] - flen + 2 - trims[a] for a in range(ndim)]
-        if min(out_ext) < 1:
-            raise ValueError("coefficients too short for this wavelet")
-        return out_ext
-
+    nlev = len(folded)
+    eng = _engine.ENGINE
+    grad_mode = torch.is_grad_enabled()
+    # the call builds a graph.  Gradients w.r.t. the coefficients only: the multi-level launches as differentiable ops
+    # (_SynthesisChain1d, _SynthesisPyramid); a learnable filter bank — `tap_t`, which implies a graph — takes the per-level ops, and so
+    # do device-resident taps.  (The separable containers' crops of the running approximation take its LEADING samples, like the
+    # reference's trims: the adjoint of a level sees a gradient of the cropped extents and treats the rest as zeros — same backward.)
+    any_grad = grad_mode and (tap_t is not None or any([t.requires_grad for t in flat]))  # (a list: one Python-level call, not one per tensor)
+    fusable = not on_device and tap_t is None
+    # ONE walk of the reference's checks per call, remembered per geometry (every band's shape: the shape checks are part of what is
+    # remembered) together with the multi-level route, which depends on the geometry only
+    hit = gkey = err = None
+    if fusable and nlev:
+        gkey = (cur.dtype, cur.shape, cur.stride(), tuple((lv[0].stride(), *[t.shape for t in lv]) for lv in folded), flen, separable)
+        hit = _rec_memo.get(gkey)
+    if hit is None:
+        exts, err = _walk_synthesis(tuple(cur.shape), folded, flen, ndim, separable)
+        hit = (exts, nlev, None)
+        if gkey is not None and err is None:  # (the fused routes are considered only when the whole walk passes)
+            if ndim == 2:
+                hit = (exts, *_pyramid_route(cur, folded, exts, flen, separable))
+            if len(_rec_memo) > 1024:
+                _rec_memo.clear()
+            _rec_memo[gkey] = hit
+    exts, upto, plan = hit
+    stop = -1 if err is None else len(exts)  # the level at which the loop below raises the reference's error
     pos = 0
-    if ndim == 1 and not separable and len(folded) >= 2 and not on_device:
-        # the coarse levels of a 1-D reconstruction in one launch (mifwt_dwt1_inv_tail) while a level's output still fits into
-        # LDS; every fused trip passes the reference's own checks first
-        differentiable = torch.is_grad_enabled() and (tap_t is not None or any(t.requires_grad for t in flat))
-        if not differentiable or tap_t is None:
-            try:
-                outs, shape = [], tuple(cur.shape)
-                for lv in range(len(folded)):
-                    ext = level_out_extent(shape, lv)
-                    outs.append(ext[0])
-                    shape = (shape[0], ext[0])
-            except (ValueError, RuntimeError, AssertionError):
-                outs = []  # the per-level loop below raises the reference's error at the level it belongs to
-            cap = 16384 if cur.dtype == torch.float32 else 8192
-            dets = [lvl[0] for lvl in folded]
-            eng = _engine.ENGINE
+    if ndim == 1 and not separable and nlev >= 2 and fusable and stop < 0:
+        # a whole 1-D reconstruction on the multi-level launches
+        outs = [e[0] for e in exts]
+        cap = 16384 if cur.dtype == torch.float32 else 8192
+        dets = [lvl[0] for lvl in folded]
 
-            def fuse(fuse, cur, a, b):  # (itself as an argument: a closure over its own name would be a reference cycle per call)
-                """Levels a .. b-1 with as few launches as possible: the finest ones in the chunked launch (mifwt_dwt1_inv_long:
-                as many as its halo rule allows), what is coarser first — chunked as well while there are too few rows for one
-                workgroup each, else in the one-workgroup-per-row launch (mifwt_dwt1_inv_tail) while the outputs fit into LDS."""
-                if b - a >= 2:
-                    y, k = eng.synthesis_long(cur, dets[a:b], rec_lo, rec_hi, outs[a:b])
+        def fuse(fuse, cur, a, b):  # (itself as an argument: a closure over its own name would be a reference cycle per call)
+            """Levels a .. b-1 with as few launches as possible: the finest ones in the chunked launch (mifwt_dwt1_inv_long:
+            as many as its halo rule allows), what is coarser first — chunked as well while there are too few rows for one
+            workgroup each, else in the one-workgroup-per-row launch (mifwt_dwt1_inv_tail) while the outputs fit into LDS."""
+            if b - a >= 2:
+                y, k = eng.synthesis_long(cur, dets[a:b], rec_lo, rec_hi, outs[a:b])
+                if y is not None:
+                    return y
+                if 2 <= k < b - a:
+                    cur = fuse(fuse, cur, a, b - k)
+                    a = b - k
+                    y, _k = eng.synthesis_long(cur, dets[a:b], rec_lo, rec_hi, outs[a:b])
                     if y is not None:
                         return y
-                    if 2 <= k < b - a:
-                        cur = fuse(fuse, cur, a, b - k)
-                        a = b - k
-                        y, _k = eng.synthesis_long(cur, dets[a:b], rec_lo, rec_hi, outs[a:b])
-                        if y is not None:
-                            return y
-                    nf = 0
-                    while a + nf < b and outs[a + nf] <= cap:
-                        nf += 1
-                    if nf >= 2:
-                        y = eng.synthesis_tail(cur, dets[a:a + nf], rec_lo, rec_hi, outs[a:a + nf])
-                        if y is not None:
-                            cur, a = y, a + nf
-                while a < b:
-                    cur = eng.synthesis(cur, folded[a], rec_lo, rec_hi, [outs[a]])
-                    a += 1
-                return cur
+                nf = 0
+                while a + nf < b and outs[a + nf] <= cap:
+                    nf += 1
+                if nf >= 2:
+                    y = eng.synthesis_tail(cur, dets[a:a + nf], rec_lo, rec_hi, outs[a:a + nf])
+                    if y is not None:
+                        cur, a = y, a + nf
+            while a < b:
+                cur = eng.synthesis(cur, folded[a], rec_lo, rec_hi, [outs[a]])
+                a += 1
+            return cur
 
-            if len(outs) == len(folded):
-                if differentiable:  # (gradients w.r.t. the coefficients only: the same launches as ONE differentiable op)
-                    cur = _SynthesisChain1d.apply(lambda a0, dd: fuse(fuse, a0, 0, len(dd)), rec_lo, rec_hi, cur, *dets)  # (fuse reads `dets`: the same tensors)
-                else:
-                    cur = fuse(fuse, cur, 0, len(folded))
-                pos = len(folded)
-    any_grad = torch.is_grad_enabled() and (tap_t is not None or any(t.requires_grad for t in flat))
-    # (gradients w.r.t. the coefficients only: the multi-level launches as differentiable ops, _SynthesisPyramid; a learnable filter
-    # bank takes the per-level ops.  The separable containers' crops of the running approximation take its LEADING samples, like the
-    # reference's trims: the adjoint of a level sees a gradient of the cropped extents and treats the rest as zeros — same backward)
-    fused_grad = any_grad and tap_t is None
-    gkey = None
-    if ndim == 2 and folded and not on_device and (not any_grad or fused_grad):
-        # geometry of the call (every band's shape: the reference's shape checks are part of what is remembered)
-        gkey = (cur.dtype, cur.shape, cur.stride(), tuple((lv[0].stride(), *[t.shape for t in lv]) for lv in folded), flen, separable)
-    # (the finest level's four coefficient planes alone must fit into LDS: 10 240 samples each at most)
-    if gkey is not None and folded[-1][0].shape[-1] * folded[-1][0].shape[-2] <= 10240:
-        # every level of a small plane in one launch, the running approximation kept on chip (mifwt_dwt2_inv_pyramid); every
-        # fused trip passes the reference's own checks first (remembered per geometry)
-        hit = _small_memo.get(gkey)
-        if hit is None:
-            try:
-                shape, out_ext = tuple(cur.shape), None
-                for lv in range(len(folded)):
-                    out_ext = level_out_extent(shape, lv)
-                    shape = (shape[0], *out_ext)
-            except (ValueError, RuntimeError, AssertionError):
-                out_ext = None  # the per-level loop below raises the reference's error at the level it belongs to
-            pl = _engine.ENGINE.synthesis_pyramid_plan(cur, folded, flen, out_ext) if out_ext is not None and cur.dtype == torch.float32 else None
-            if len(_small_memo) > 1024:
-                _small_memo.clear()
-            hit = _small_memo[gkey] = (out_ext, pl)
-        out_ext, pl = hit
-        if pl is not None and pl[3]:
-            if fused_grad:
-                y = _SynthesisPyramid.apply(rec_lo, rec_hi, tuple(out_ext), pl, len(folded), cur, *[t for lv in folded for t in lv])
-            else:
-                y = _engine.ENGINE.synthesis_pyramid(cur, folded, rec_lo, rec_hi, out_ext, plan=pl)
-            if y is not None:
-                return layout.unfold(y)
-    # big planes: the FINEST up to three levels (that is where the bytes are) in one streaming launch (mifwt_dwt2_inv_pyramid's
-    # second kernel); what is coarser goes first, through the loop below.  `tail` = how many levels that launch takes (0: none).
-    # The decision depends on the geometry only and is remembered per geometry.
-    tail, tail_ext, tail_plan = 0, None, None
-    if gkey is not None and cur.dtype == torch.float32 and folded[-1][0].shape[-1] * folded[-1][0].shape[-2] > 10240:
-        tkey = gkey
-        hit = _tail_memo.get(tkey)
-        if hit is None:
-            hit = (0, None, None)
-            try:
-                shapes, shape = [], tuple(cur.shape)
-                for lv in range(len(folded)):
-                    shapes.append(shape)
-                    shape = (shape[0], *level_out_extent(shape, lv))
-                final_ext = shape[1:]
-            except (ValueError, RuntimeError, AssertionError):
-                shapes = None  # the per-level loop below raises the reference's error at the level it belongs to
-            if shapes is not None:
-                for k in (3, 2, 1):
-                    if k > len(folded):
-                        continue
-                    first = len(folded) - k
-                    if first == 0:
-                        a0 = cur
-                    else:  # the approximation the coarser levels will hand over: dense, cropped to the level's band extents
-                        ext = tuple(min(c, s_) for c, s_ in zip(shapes[first], folded[first][0].shape)) if separable else shapes[first]
-                        a0 = torch.empty(ext, dtype=cur.dtype, device="meta")
-                    if separable and first == 0:
-                        a0 = a0[tuple(slice(0, s_) for s_ in folded[0][0].shape)]
-                    pl = _engine.ENGINE.synthesis_pyramid_plan(a0, folded[first:], flen, final_ext)
-                    if pl is not None and pl[3] == 2:
-                        hit = (k, final_ext, pl)
-                        break
-            if len(_tail_memo) > 1024:
-                _tail_memo.clear()
-            _tail_memo[tkey] = hit
-        tail, tail_ext, tail_plan = hit
-    while pos < len(folded):
+        if any_grad:  # (the same launches as ONE differentiable op)
+            cur = _SynthesisChain1d.apply(lambda a0, dd: fuse(fuse, a0, 0, len(dd)), rec_lo, rec_hi, cur, *dets)  # (fuse reads `dets`: the same tensors)
+        else:
+            cur = fuse(fuse, cur, 0, nlev)
+        pos = nlev
+    while pos < nlev:
         det = folded[pos]
         if separable:
             cur = cur[tuple(slice(0, s_) for s_ in det[0].shape)]
-        if tail and pos == len(folded) - tail:
-            # (the plan was made for a dense hand-over approximation; a strided one — a separable crop — is looked up afresh)
+        if pos == stop:
+            raise err
+        if pos == upto:
+            # the rest in one launch (the plan was made for a dense hand-over approximation; a strided one — a separable crop — is
+            # looked up afresh)
             same = pos == 0 or cur.is_contiguous()
-            if fused_grad:
-                y = _SynthesisPyramid.apply(rec_lo, rec_hi, tuple(tail_ext), tail_plan if same else None, len(folded) - pos, cur,
+            if any_grad:
+                y = _SynthesisPyramid.apply(rec_lo, rec_hi, tuple(exts[-1]), plan if same else None, nlev - pos, cur,
                                             *[t for lv in folded[pos:] for t in lv])
             else:
-                y = _engine.ENGINE.synthesis_pyramid(cur, folded[pos:], rec_lo, rec_hi, tail_ext, plan=tail_plan if same else None)
+                y = eng.synthesis_pyramid(cur, folded[pos:], rec_lo, rec_hi, exts[-1], plan=plan if same else None)
             if y is not None:
                 return layout.unfold(y)
-            tail = 0  # (bands that do not share their strides: level by level)
-        out_ext = level_out_extent(tuple(cur.shape), pos)
-        differentiable = torch.is_grad_enabled() and (cur.requires_grad or any(t.requires_grad for t in det) or tap_t is not None)
+            upto = nlev  # (bands that do not share their strides: level by level)
+        # PER LEVEL: a coarse level whose inputs need no gradient is a plain call even when a finer level's details require one
+        differentiable = grad_mode and (cur.requires_grad or any(t.requires_grad for t in det) or tap_t is not None)
         # levels go in pairs counted from the FINEST one of those left to this loop (that is where the bytes are): an odd count
         # starts with a single level
-        if (ndim == 2 and not differentiable and not on_device and (len(folded) - tail - pos) % 2 == 0 and len(folded) - tail - pos >= 2
-                and not (torch.is_grad_enabled() and any(t.requires_grad for t in folded[pos + 1]))):
+        left = upto - pos
+        if (ndim == 2 and not differentiable and not on_device and left % 2 == 0 and left >= 2
+                and not (grad_mode and any(t.requires_grad for t in folded[pos + 1]))):
             # two levels per launch, the approximation between them kept on chip (mifwt_dwt2_inv_pair); the checks of the
-            # second trip are the reference's own and run before anything is launched.  Separable containers: the crop of the
+            # second trip are the reference's own and come before anything is launched.  Separable containers: the crop of the
             # running approximation to the next detail shape IS the extent the kernel synthesises the approximation tile for
-            out_ext2 = level_out_extent((cur.shape[0], *out_ext), pos + 1)
-            y = _engine.ENGINE.synthesis_pair(cur, det, folded[pos + 1], rec_lo, rec_hi, out_ext2)
+            if pos + 1 == stop:
+                raise err
+            y = eng.synthesis_pair(cur, det, folded[pos + 1], rec_lo, rec_hi, exts[pos + 1])
             if y is not None:
                 cur = y
                 pos += 2
                 continue
         if differentiable:
-            cur = _SynthesisLevel.apply(rec_lo, rec_hi, tuple(out_ext), *((tap_t[2], tap_t[3]) if tap_t else (None, None)), cur, *det)
+            cur = _SynthesisLevel.apply(rec_lo, rec_hi, tuple(exts[pos]), *_graph_taps(tap_t, 2), cur, *det)
         else:
-            cur = _engine.ENGINE.synthesis(cur, det, rec_lo, rec_hi, out_ext)
+            cur = eng.synthesis(cur, det, rec_lo, rec_hi, exts[pos])
         pos += 1
     return layout.unfold(cur)
 

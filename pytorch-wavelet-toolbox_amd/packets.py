@@ -157,7 +157,7 @@ class _PacketTree(collections.UserDict):
         _fwt._check_pad(flat.shape[1:], len(dec_lo), "reflect" if self.mode is None else self.mode)
         tap_t = _fwt._tap_tensors(self.wavelet)  # learnable filter bank: the taps stay in the graph (src/ptwt/_util.py:115-132)
         if torch.is_grad_enabled() and (flat.requires_grad or tap_t is not None):
-            out = _fwt._AnalysisLevel.apply(flat, dec_lo, dec_hi, mode_id, *((tap_t[0], tap_t[1]) if tap_t else (None, None)))
+            out = _fwt._AnalysisLevel.apply(flat, dec_lo, dec_hi, mode_id, *_fwt._graph_taps(tap_t, 0))
         else:
             out = _engine.ENGINE.analysis(flat, dec_lo, dec_hi, mode_id)  # [B * nb^level, nb, M..]
         self._store_level(level + 1, out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:]))
@@ -264,7 +264,7 @@ class _PacketTree(collections.UserDict):
                         out_ext[a] = target[a]
             approx, details = flat[:, 0], [flat[:, s] for s in range(1, nb)]
             if torch.is_grad_enabled() and (flat.requires_grad or tap_t is not None):
-                rec = _fwt._SynthesisLevel.apply(rec_lo, rec_hi, tuple(out_ext), *((tap_t[2], tap_t[3]) if tap_t else (None, None)), approx, *details)
+                rec = _fwt._SynthesisLevel.apply(rec_lo, rec_hi, tuple(out_ext), *_fwt._graph_taps(tap_t, 2), approx, *details)
             else:
                 rec = _engine.ENGINE.synthesis(approx, details, rec_lo, rec_hi, out_ext)
             buf = rec.reshape(children.shape[0], *([nb] * level), *rec.shape[1:])

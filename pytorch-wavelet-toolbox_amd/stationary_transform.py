@@ -102,10 +102,7 @@ class _Swt1(torch.autograd.Function):
         x, lo_t, hi_t = ctx.saved_tensors
         dilation, scale = ctx.meta
         g_x = _Iswt1.apply(g[:, 0], g[:, 1], _rev(lo_t), _rev(hi_t), dilation, scale) if ctx.needs_input_grad[0] else None
-        t_lo = t_hi = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            t_lo, t_hi = _Swt1Corr.apply(x, g, lo_t.numel(), dilation, scale)
-            t_lo, t_hi = _fwt._like(t_lo, lo_t), _fwt._like(t_hi, hi_t)
+        t_lo, t_hi = _fwt._tap_pair(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], _Swt1Corr, lo_t, hi_t, x, g, lo_t.numel(), dilation, scale)
         return g_x, t_lo, t_hi, None, None
 
 
@@ -124,10 +121,7 @@ class _Iswt1(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gb = _Swt1.apply(g_y, _rev(lo_t), _rev(hi_t), dilation, scale)
             g_a, g_d = gb[:, 0], gb[:, 1]
-        t_lo = t_hi = None
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            t_lo, t_hi = _Iswt1Corr.apply(a, d, g_y, lo_t.numel(), dilation, scale)
-            t_lo, t_hi = _fwt._like(t_lo, lo_t), _fwt._like(t_hi, hi_t)
+        t_lo, t_hi = _fwt._tap_pair(ctx.needs_input_grad[2] or ctx.needs_input_grad[3], _Iswt1Corr, lo_t, hi_t, a, d, g_y, lo_t.numel(), dilation, scale)
         return g_a, g_d, t_lo, t_hi, None, None
 
 
@@ -330,7 +324,7 @@ def swt(data: torch.Tensor, wavelet: Union[Wavelet, str], level: Optional[int] =
     cur = x
     for lvl in range(level):
         if torch.is_grad_enabled() and (cur.requires_grad or tap_t is not None):
-            buf = _SwtLevel.apply(cur, dec_lo, dec_hi, 2 ** lvl, 1.0, *((tap_t[0], tap_t[1]) if tap_t else (None, None)))
+            buf = _SwtLevel.apply(cur, dec_lo, dec_hi, 2 ** lvl, 1.0, *_fwt._graph_taps(tap_t, 0))
         else:
             buf = _level_fwd(cur, dec_lo, dec_hi, 2 ** lvl, 1.0)
         out.append(layout.unfold(buf[:, 1]))
@@ -360,7 +354,7 @@ def iswt(coeffs: Sequence[torch.Tensor], wavelet: Union[Wavelet, str], *, axis: 
         if det.shape != cur.shape:
             raise RuntimeError("stack expects each tensor to be equal size")  # torch.stack in the reference (:146)
         if torch.is_grad_enabled() and (cur.requires_grad or det.requires_grad or tap_t is not None):
-            cur = _IswtLevel.apply(cur, det, rec_lo, rec_hi, dilation, 0.5, *((tap_t[2], tap_t[3]) if tap_t else (None, None)))
+            cur = _IswtLevel.apply(cur, det, rec_lo, rec_hi, dilation, 0.5, *_fwt._graph_taps(tap_t, 2))
         else:
             cur = _level_inv(cur, det, rec_lo, rec_hi, dilation, 0.5)
     return layout.unfold(cur)

@@ -180,7 +180,11 @@ class Recorder:
         self._inputs = [t for t in inputs if isinstance(t, torch.Tensor)]
         self._launches, self._tracked = [], []
         del self._queries[:]
-        out = fn(*inputs)
+        out = err = None
+        try:
+            out = fn(*inputs)
+        except (ValueError, RuntimeError, AssertionError) as e:  # (a case that pins an error: the launches made before it, its type and text)
+            err = e
         flat = []
 
         def walk(o):
@@ -214,6 +218,8 @@ class Recorder:
         rec = {"launches": finish(self._launches), "queries": list(self._queries),
                "returns": [None if out is None else "no tensor"] if not flat else
                [[list(r.shape), list(r.stride()), str(r.dtype).replace("torch.", "")] for r in flat]}
+        if err is not None:
+            rec["raises"] = [type(err).__name__, str(err)]
         self.records.setdefault(case, []).append(rec)
         self._tracked = []
         return out
@@ -361,6 +367,82 @@ def run_cases(r: Recorder) -> None:
         r.call("force-generic-after", lambda t: P.wavedec2(t, "db4", level=2, mode="reflect"), [x])
     finally:
         E.set_option(E.OPT_FORCE_GENERIC, 0)
+    grad_cases(case, P, _wavelets)
+
+
+def grad_cases(case, P, _wavelets) -> None:
+    """Gradient-mode calls: the autograd routes of ``_fwt.py``.  Each case is one function that runs the forward and one
+    ``torch.autograd.grad`` of the sum of its outputs; the record holds the launches of both."""
+
+    def tensors(o):
+        if isinstance(o, torch.Tensor):
+            return [o]
+        return [t for e in (o.values() if isinstance(o, dict) else o) for t in tensors(e)]
+
+    def leaf(t):
+        return torch.zeros_like(t).requires_grad_(True)
+
+    def grad_of(forward, wrt=None, **gkw):
+        def fn(*ts):
+            out = forward(*ts)
+            leaves = [t for t in ts if t.requires_grad] if wrt is None else [ts[i] for i in wrt]
+            return out, torch.autograd.grad(sum(t.sum() for t in tensors(out) if t.requires_grad), leaves, **gkw)
+
+        return fn
+
+    def coeffs(dec, x, *a, **kw):  # (shapes of a decomposition, for the reconstruction cases: not part of any record)
+        with torch.no_grad():
+            return dec(x, *a, **kw)
+
+    def rebuild_like(c):
+        """flat tensors -> the container ``c`` has"""
+        def build(ts):
+            it = iter(ts)
+            out = [({k: next(it) for k in lv} if isinstance(lv, dict) else type(lv)(*[next(it) for _ in lv]) if isinstance(lv, tuple) else next(it))
+                   for lv in c]
+            return out if isinstance(c, list) else tuple(out)
+
+        return build
+
+    def rec_case(name, rec, c, wavelet, needs=None, **gkw):
+        flat = tensors(c)
+        ins = [leaf(t) if needs is None or i in needs else torch.zeros_like(t) for i, t in enumerate(flat)]
+        build = rebuild_like(c)
+        case(name, grad_of(lambda *ts: rec(build(ts), wavelet), **gkw), *ins)
+
+    # 1-D: the tail launch, the long launches, forward and fused chain backward
+    x = _z(3, 1001).requires_grad_(True)
+    case("grad-wavedec-tail", grad_of(lambda t: P.wavedec(t, "db5", level=3, mode="reflect")), x)
+    rec_case("grad-waverec-tail", P.waverec, coeffs(P.wavedec, x, "db5", level=3, mode="reflect"), "db5")
+    x = _z(2, 300000).requires_grad_(True)
+    case("grad-wavedec-long", grad_of(lambda t: P.wavedec(t, "db5", level=6, mode="symmetric")), x)
+    rec_case("grad-waverec-long", P.waverec, coeffs(P.wavedec, x, "db5", level=6, mode="symmetric"), "db5")
+    # 2-D: the whole reconstruction of a small plane in one launch (with and without a graph of the backward), the per-level route
+    c = coeffs(P.wavedec2, _z(5, 40, 36), "db2", level=3, mode="symmetric")
+    rec_case("grad-waverec2-small-planes", P.waverec2, c, "db2")
+    rec_case("grad-waverec2-small-planes-create-graph", P.waverec2, c, "db2", create_graph=True)
+    x = _z(2, 40, 300).requires_grad_(True)
+    case("grad-wavedec2-per-level", grad_of(lambda t: P.wavedec2(t, "db3", level=2, mode="reflect")), x)
+    c = coeffs(P.wavedec2, x, "db3", level=2, mode="reflect")
+    rec_case("grad-waverec2-per-level", P.waverec2, c, "db3")
+    # only the finest level's details ask for a gradient: the coarse level is a plain call, the fine one the differentiable op
+    rec_case("grad-waverec2-finest-details-only", P.waverec2, c, "db3", needs=(4, 5, 6))
+    # a learnable filter bank: the per-level ops and the tap correlations
+    bank = [torch.tensor(t, dtype=torch.float32, requires_grad=True) for t in _wavelets.host_taps("db2")]
+    case("grad-wavedec2-learnable-bank", grad_of(lambda t, *b: P.wavedec2(t, tuple(b), level=2, mode="symmetric"), wrt=(0, 1, 2)),
+         _z(2, 40, 36).requires_grad_(True), *bank)
+    # the separable crop (an odd extent: the running approximation is one sample larger than the next level's details), and 3-D
+    rec_case("grad-fswaverec2-odd-extent", P.fswaverec2, coeffs(P.fswavedec2, _z(2, 33, 41), "db2", level=2, mode="zero"), "db2")
+    case("grad-wavedec3", grad_of(lambda t: P.wavedec3(t, "db2", level=2, mode="reflect")), _z(2, 12, 14, 20).requires_grad_(True))
+    # coefficients that fail a check of the reference at the second level: the launches made before the error, its type and text
+    c = coeffs(P.wavedec, _z(3, 1001), "db5", level=3, mode="reflect")
+    case("error-waverec-second-level", lambda *ts: P.waverec(list(ts), "db5"), c[0], c[1], c[2], _z(3, c[3].shape[1] + 5))
+    c = coeffs(P.wavedec2, _z(2, 40, 300), "db3", level=3, mode="reflect")
+    bad = (c[0], c[1], type(c[2])(c[2][0], c[2][1], _z(2, c[2][2].shape[1], c[2][2].shape[2] + 1)), c[3])
+    case("error-waverec2-second-level", lambda *ts: P.waverec2(rebuild_like(bad)(ts), "db3"), *tensors(bad))
+    c = coeffs(P.wavedec2, _z(2, 40, 300), "db3", level=2, mode="reflect")  # (two levels go as a pair: its look-ahead raises before the launch)
+    bad = (c[0], c[1], type(c[2])(c[2][0], c[2][1], _z(2, c[2][2].shape[1], c[2][2].shape[2] + 1)))
+    case("error-waverec2-pair-look-ahead", lambda *ts: P.waverec2(rebuild_like(bad)(ts), "db3"), *tensors(bad))
 
 
 def bound_launch_entries(real) -> set:

@@ -3,7 +3,8 @@
 The cases, the recording stand-in for the library and the stubs that let CPU tensors reach the launch live in
 tests/golden/make_engine_calls.py, which also wrote the fixture; this module runs the same cases on the modules of the tree and
 compares exactly: per launch the entry name, the bytes of every descriptor, every scalar, the contents of every tap / integer array
-and every pointer as (tensor, byte offset); per call what it returned (shapes, strides, dtypes) and the host queries it made.
+and every pointer as (tensor, byte offset); per call what it returned (shapes, strides, dtypes), the host queries it made and, for
+the cases that pin an error, its type and text.  The gradient-mode cases run a forward and one ``torch.autograd.grad`` each.
 ``record()`` itself asserts the coverage condition (the recorded entry names are the launch entry points the modules bind), the cache
 hit of a repeated geometry, the plans dropped by ``set_option`` and the refused 1-D tails.
 """
@@ -41,3 +42,4 @@ def test_library_calls(got, case):
             assert lh["args"] == lw["args"], lh["entry"]
         assert h["returns"] == w["returns"]
         assert h["queries"] == w["queries"]
+        assert h.get("raises") == w.get("raises")  # (a case that pins an error: its type and text)

@@ -791,6 +791,24 @@ def test_differentiable_calls_take_the_multi_level_ops_host_side(oracle_engine):
         assert abs(lhs - sum((g * t.detach()).sum().item() for g, t in zip(gl, leaves))) < 1e-3 * max(1.0, abs(lhs))
 
 
+def test_multi_level_routes_equal_the_recorded_trace():
+    """Which engine calls the multi-level drivers and autograd ops of `_fwt` make, with the shapes of their tensor arguments, against
+    tests/golden/fwt_route_trace.json (written by tests/golden/make_fwt_route_trace.py, which holds the table and the tracing stand-in):
+    wavedec2 / waverec2 / wavedec / waverec / fswavedec2 / fswaverec2, graph-free, gradient w.r.t. the input and the same with
+    create_graph=True, zero and symmetric mode, each geometry a first time and again.  The stand-in serves `pyramid_levels`, so
+    `_AnalysisPyramid` with its one-launch zero-mode backward and the fused 2-D backward of `_SynthesisPyramid` are in the trace."""
+    import json
+
+    from tests.golden import make_fwt_route_trace as T
+
+    with open(T.FIXTURE) as f:
+        want = json.load(f)
+    got = T.record()
+    assert sorted(got) == sorted(want)
+    for key in sorted(want):
+        assert got[key] == want[key], key
+
+
 def test_every_kernel_id_is_documented_in_the_header():
     """`enum KernelId` (csrc/mifwt_common.h) against the kernel-id list in the comment of `mifwt_kernel_id` (include/mifwt.h): a new
     kernel family must appear in the public header."""
