@@ -343,6 +343,39 @@ int mifwt_swt2_inv(int dtype, int filt_len, int64_t images, int64_t H, int64_t W
                    int64_t y_row_stride, const double* row_lo, const double* row_hi, const double* col_lo, const double* col_hi,
                    double scale, void* stream);
 
+/* 3-D stationary levels (swt3 / iswt3 of the package: the 1-D level above along the three axes of a volume, pywt.swtn with
+ * trim_approx=True, norm=False by construction) in ONE launch per level that writes every output once and keeps no intermediate
+ * volume in global memory (kernel ids 36 / 37, csrc/mifwt_swt3.hip: a workgroup walks down the a-trous lattice of slices; axis -1
+ * from global memory into an LDS tile of lattice rows, axis -2 from LDS, axis -3 in a register ring).  `volumes` volumes of Dz slices
+ * of H rows of W contiguous samples; every operand has its own volume, slice and row stride in elements (level j + 1 can read plane 0
+ * of level j's [B, 8, Dz, H, W] buffer, slices need no copy); outputs must not overlap inputs.  Periodic in all three axes with any
+ * number of wraps (any Dz, H, W >= 1, any dilation >= 1).  taps[0..5] = w_lo, w_hi (along W, axis -1), h_lo, h_hi (along H, axis
+ * -2), z_lo, z_hi (along Dz, axis -3), filt_len doubles each.  Band q = 4 [axis -3 high] + 2 [axis -2 high] + [axis -1 high]: aaa,
+ * aad, ada, add, daa, dad, dda, ddd.  `scale` multiplies the result: 1 for swt3, 0.125 for iswt3; with all six filters reversed and
+ * the same scale each call is the adjoint of the other.
+ *   fwd: bands[q][s][r][n] = scale sum_k z[k] sum_m h[m] sum_t w[t] x[(s + D (L/2 - k)) mod Dz][(r + D (L/2 - m)) mod H][(n + D (L/2 - t)) mod W]
+ *        with (z, h, w) the low- or high-pass filter of each axis as the bits of q say
+ *   inv: y[s][r][n] = scale sum_q sum_k z[k] sum_m h[m] sum_t w[t] bands[q][(s + D (L/2 - 1 - k)) mod Dz][(r + D (L/2 - 1 - m)) mod H][(n + D (L/2 - 1 - t)) mod W]
+ * LIMIT: compile-time lengths only: even filt_len 2 .. 10, f32 / f64, extents and dilation * filt_len below 2^28.
+ * mifwt_swt3_supported answers 1 where the two entries run and 0 where they answer MIFWT_ERR_UNSUPPORTED (longer filters, f16): the
+ * caller then composes the level from mifwt_swt2_* and mifwt_swt_*.  MIFWT_OPT_ROWS_PER_CHUNK > 0 overrides the lattice slices per
+ * workgroup.  mifwt_swt3_plan (diagnostics and tests; host code, launches nothing) writes the work split of such a launch into
+ * out[0 .. MIFWT_SWT3_PLAN_INTS): slice residues, row residues, slice segments, lattice slices per segment, row tiles, column
+ * strips, tile rows RT, tile rows per lane RW, columns per lane E, LDS bytes, threads per workgroup; a workgroup per (volume, slice
+ * residue, row residue, segment, row tile, strip), a strip = 64 E columns.  Returns the number of ints written or an error. */
+#define MIFWT_SWT3_PLAN_INTS 11
+int mifwt_swt3_supported(int dtype, int filt_len, int64_t volumes, int64_t Dz, int64_t H, int64_t W, int64_t dilation);
+int mifwt_swt3_fwd(int dtype, int filt_len, int64_t volumes, int64_t Dz, int64_t H, int64_t W, int64_t dilation, const void* x,
+                   int64_t x_volume_stride, int64_t x_slice_stride, int64_t x_row_stride, void* const* bands,
+                   const int64_t* band_volume_strides, const int64_t* band_slice_strides, const int64_t* band_row_strides,
+                   const double* const* taps, double scale, void* stream);
+int mifwt_swt3_inv(int dtype, int filt_len, int64_t volumes, int64_t Dz, int64_t H, int64_t W, int64_t dilation,
+                   const void* const* bands, const int64_t* band_volume_strides, const int64_t* band_slice_strides,
+                   const int64_t* band_row_strides, void* y, int64_t y_volume_stride, int64_t y_slice_stride, int64_t y_row_stride,
+                   const double* const* taps, double scale, void* stream);
+int mifwt_swt3_plan(int dtype, int filt_len, int inverse, int64_t volumes, int64_t Dz, int64_t H, int64_t W, int64_t dilation, int* out,
+                    int capacity);
+
 /* BOUNDARY-WAVELET levels — the padding-free transforms ptwt.MatrixWavedec / MatrixWaverec (src/ptwt/matmul_transform.py:409-430: pad one
  * sample if odd + torch.sparse.mm(A, x) + split; :679-703: cat + torch.sparse.mm(S, c) + drop the pad sample) and, in their separable
  * form, MatrixWavedec2 / MatrixWaverec2 (src/ptwt/matmul_transform_2.py:514-529: A_rows X A_cols^T through two transposes + splits;
@@ -520,7 +553,7 @@ int mifwt_set_option(int key, int value);
 int mifwt_pyr_profile_buffer(void* device_buffer);
 
 /* Diagnostic: how many launches of a kernel VARIANT this process has enqueued — variants that share a kernel id (what the tests use to
- * pin "this code path ran"; `variant` out of range: 0).  Values below 16 are variants; the 2-D stationary kernels, which have no
+ * pin "this code path ran"; `variant` out of range: 0).  Values below 16 are variants; the 2-D and 3-D stationary kernels, which have no
  * variants, are counted under their kernel ids. */
 #define MIFWT_VARIANT_FWD_MFMA_WALK 0 /* id 11: the analysis kernel that walks down column panels */
 #define MIFWT_VARIANT_FWD_MFMA_TILE 1 /* id 11: the tile-at-a-time analysis kernel of round 2 (MIFWT_OPT_MFMA_MODE 3) */
@@ -528,6 +561,8 @@ int mifwt_pyr_profile_buffer(void* device_buffer);
 #define MIFWT_VARIANT_FWD_PYR_ST8 3   /* id 16: 8-byte stores (any row pitch) */
 #define MIFWT_KERNEL_SWT2_FWD 34       /* id 34: fused 2-D stationary analysis level (mifwt_swt2_fwd) */
 #define MIFWT_KERNEL_SWT2_INV 35       /* id 35: fused 2-D stationary synthesis level (mifwt_swt2_inv) */
+#define MIFWT_KERNEL_SWT3_FWD 36       /* id 36: fused 3-D stationary analysis level (mifwt_swt3_fwd) */
+#define MIFWT_KERNEL_SWT3_INV 37       /* id 37: fused 3-D stationary synthesis level (mifwt_swt3_inv) */
 #define MIFWT_LAUNCH_COUNTERS 64
 unsigned long long mifwt_launch_count(int variant);
 

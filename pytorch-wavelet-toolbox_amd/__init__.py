@@ -24,7 +24,7 @@ from .conv_transform import wavedec, waverec
 from .conv_transform_2 import wavedec2, waverec2
 from .conv_transform_3 import wavedec3, waverec3
 from .packets import WaveletPacket, WaveletPacket2D
-from .stationary_transform import iswt, iswt2, swt, swt2
+from .stationary_transform import iswt, iswt2, iswt3, swt, swt2, swt3
 from .matmul_transform import MatrixWavedec, MatrixWaverec
 from .matmul_transform_2 import MatrixWavedec2, MatrixWaverec2
 from .matmul_transform_3 import MatrixWavedec3, MatrixWaverec3
@@ -60,6 +60,8 @@ __all__ = [
     "iswt",
     "swt2",
     "iswt2",
+    "swt3",
+    "iswt3",
     "WaveletPacket2D",
     "MatrixWavedec",
     "MatrixWaverec",

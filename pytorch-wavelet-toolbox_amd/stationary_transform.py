@@ -1,5 +1,6 @@
-"""Stationary (undecimated) wavelet transform: ``swt`` / ``iswt`` (API of reference src/ptwt/stationary_transform.py) and their 2-D
-forms ``swt2`` / ``iswt2`` (``pywt.swt2`` / ``pywt.iswt2``; the reference has none).
+"""Stationary (undecimated) wavelet transform: ``swt`` / ``iswt`` (API of reference src/ptwt/stationary_transform.py), their 2-D
+forms ``swt2`` / ``iswt2`` (``pywt.swt2`` / ``pywt.iswt2``; the reference has none) and their 3-D forms ``swt3`` / ``iswt3``
+(``pywt.swtn`` / ``pywt.iswtn`` over three axes).
 
 Equivalent to ``pywt.swt(..., trim_approx=True, norm=False)`` like the reference.  Each level is one HIP kernel
 (C ABI ``mifwt_swt_fwd`` / ``mifwt_swt_inv``): stride-1 filter bank with dilation ``2^level`` and the periodic
@@ -11,6 +12,11 @@ A 2-D level is the 1-D level along both axes of a plane.  It runs as ONE fused l
 csrc/mifwt_swt2.hip: 1 plane in and 4 out, no intermediate plane, no transposed copy) where ``mifwt_swt2_supported`` says so, and
 otherwise — filters longer than 20 taps, learnable filter banks — on the COMPOSED route: the 1-D level ops along the last axis, then
 along the other one on permuted copies.  ``FORCE_COMPOSED`` selects that route for every call (cross-checks, timing baseline).
+
+A 3-D level is the 1-D level along the three axes of a volume: ONE fused launch (``mifwt_swt3_fwd`` / ``mifwt_swt3_inv``,
+csrc/mifwt_swt3.hip: 1 volume in and 8 out, no intermediate volume) where ``mifwt_swt3_supported`` says so — even lengths up to 10 —
+and otherwise (longer filters, learnable banks, ``FORCE_COMPOSED``, the cells of ``COMPOSED3_CELLS``) composed from the 2-D level on
+every depth slice and the 1-D level ops along depth on permuted copies.
 """
 from __future__ import annotations
 
@@ -22,9 +28,9 @@ import torch
 
 from . import _engine, _fwt
 from ._wavelets import host_taps
-from .constants import Wavelet, WaveletCoeff2d, WaveletDetailTuple2d
+from .constants import Wavelet, WaveletCoeff2d, WaveletCoeffNd, WaveletDetailTuple2d
 
-__all__ = ["swt", "iswt", "swt2", "iswt2"]
+__all__ = ["swt", "iswt", "swt2", "iswt2", "swt3", "iswt3"]
 
 _i64, _vp, _dbl_p = ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 _vp4, _i64x4 = ctypes.c_void_p * 4, ctypes.c_int64 * 4
@@ -52,7 +58,30 @@ def _swt2_entries():
     return lib
 
 
+# the fused 3-D levels likewise (``_swt3_entries``)
+_vp8, _i64x8, _dbl_p6 = ctypes.c_void_p * 8, ctypes.c_int64 * 8, _dbl_p * 6
+SWT3_PLAN_INTS = 11  # MIFWT_SWT3_PLAN_INTS
+_SWT3_LAUNCHES = {
+    "mifwt_swt3_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64, _i64]),
+    "mifwt_swt3_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp8, _i64x8, _i64x8,
+                                      _i64x8, _dbl_p6, ctypes.c_double, _vp]),
+    "mifwt_swt3_inv": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, _vp8, _i64x8, _i64x8, _i64x8, _vp, _i64, _i64,
+                                      _i64, _dbl_p6, ctypes.c_double, _vp]),
+    "mifwt_swt3_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.c_int]),
+}
+
+
+def _swt3_entries():
+    """The loaded library with ``mifwt_swt3_supported`` / ``_fwd`` / ``_inv`` / ``_plan`` bound (once)."""
+    lib = _engine.load_library()
+    if getattr(lib.mifwt_swt3_fwd, "argtypes", None) is None:
+        _engine.register_entries(_SWT3_LAUNCHES)
+    return lib
+
+
 KID_SWT2, KID_ISWT2 = 34, 35  # kernel ids of the fused 2-D levels (``_engine.launch_count`` counts them under these ids)
+KID_SWT3, KID_ISWT3 = 36, 37  # kernel ids of the fused 3-D levels
 _rows = _engine._unit_last  # [B, N] with contiguous samples (row stride free)
 
 
@@ -597,4 +626,240 @@ def iswt2(coeffs: WaveletCoeff2d, wavelet: Union[Wavelet, str], *, axes: Tuple[i
             cur = _Iswt2Level.apply(*bands, taps, dilation, 0.25)
         else:
             cur = _level2_inv(bands, taps, dilation, 0.25)
+    return layout.unfold(cur)
+
+
+# ---- 3-D levels ---------------------------------------------------------------------------------------------------------------------------
+# A level takes SIX filters (w_lo, w_hi along the last axis; h_lo, h_hi along the one before it; z_lo, z_hi along depth): the transforms
+# pass the wavelet's pair three times, the tests pass six different ones.  Planes of a level buffer [B, 8, Dz, H, W]: plane
+# 4 [depth high] + 2 [axis -2 high] + [axis -1 high] — aaa, aad, ada, add, daa, dad, dda, ddd, the keys of wavedec3 in their order.
+# (direction "fwd" / "inv", dtype, filter length) cells that stay on the composed route because the fused launch did not beat it
+# there (tools/swt3_bench.py, EXPERIMENTS.md part S): the project's rule for every fused kernel.
+COMPOSED3_CELLS: set = set()
+Taps6 = Tuple[Sequence[float], Sequence[float], Sequence[float], Sequence[float], Sequence[float], Sequence[float]]
+_KEYS3 = _fwt._KEYS_ND[3]
+
+
+def _fused3(direction: str, dtype: torch.dtype, flen: int, b: int, dz: int, h: int, w: int, dilation: int) -> bool:
+    """Does the fused 3-D launch serve this level?  (``mifwt_swt3_supported``: float32 / float64, even lengths up to 10.)"""
+    if FORCE_COMPOSED or dtype not in (torch.float32, torch.float64) or (direction, dtype, flen) in COMPOSED3_CELLS:
+        return False
+    return bool(_swt3_entries().mifwt_swt3_supported(_engine._DTYPE_IDS[dtype], flen, b, dz, h, w, dilation))
+
+
+def _merged6(taps: Taps6, dilation: int, dz: int, h: int, w: int) -> Taps6:
+    """:func:`_merge_aliased` per axis: each of the six filters against the extent it runs along."""
+    return tuple(_merge_aliased(t, dilation, n) for t, n in zip(taps, (w, w, h, h, dz, dz)))
+
+
+def _composed3_fwd(x: torch.Tensor, taps: Taps6, dilation: int, scale: float, tap_t=None) -> torch.Tensor:
+    """The level from what exists: the 2-D level on every depth slice ([B Dz, H, W]), then the 1-D level op along depth on a permuted
+    copy.  Differentiable (data, and the taps when ``tap_t`` = the six tap tensors is given) when grad mode is on."""
+    b, dz, h, w = x.shape
+    diff = torch.is_grad_enabled() and (x.requires_grad or tap_t is not None)
+    planes = x.reshape(b * dz, h, w)
+    if tap_t is not None:
+        p2 = _composed2_fwd(planes, taps[:4], dilation, 1.0, tuple(tap_t[:4]))
+    elif diff:
+        p2 = _Swt2Level.apply(planes, tuple(taps[:4]), dilation, 1.0)
+    else:
+        p2 = _level2_fwd(planes, taps[:4], dilation, 1.0)
+    # [B Dz, 2 [axis -1 high] + [axis -2 high], H, W] -> depth last
+    lines = p2.reshape(b, dz, 4, h, w).permute(0, 2, 3, 4, 1).reshape(b * 4 * h * w, dz)
+    if diff:
+        zt = (tap_t[4], tap_t[5]) if tap_t is not None else (None, None)
+        cols = _SwtLevel.apply(lines, taps[4], taps[5], dilation, scale, *zt)
+    else:
+        cols = _level_fwd(lines, taps[4], taps[5], dilation, scale)
+    # [B, axis -1 band, axis -2 band, H, W, depth band, Dz] -> [B, 4 depth + 2 (axis -2) + (axis -1), Dz, H, W]
+    return cols.reshape(b, 2, 2, h, w, 2, dz).permute(0, 5, 2, 1, 6, 3, 4).reshape(b, 8, dz, h, w)
+
+
+def _composed3_inv(bands: Sequence[torch.Tensor], taps: Taps6, dilation: int, scale: float, tap_t=None) -> torch.Tensor:
+    """V_cb = S_depth(band_a,cb, band_d,cb) from the 1-D synthesis level op on permuted copies, then the 2-D synthesis level of the four
+    V on every depth slice."""
+    b, dz, h, w = bands[0].shape
+    diff = torch.is_grad_enabled() and (any(t.requires_grad for t in bands) or tap_t is not None)
+    lows = torch.stack(tuple(bands[:4])).permute(0, 1, 3, 4, 2).reshape(4 * b * h * w, dz)
+    highs = torch.stack(tuple(bands[4:])).permute(0, 1, 3, 4, 2).reshape(4 * b * h * w, dz)
+    if diff:
+        zt = (tap_t[4], tap_t[5]) if tap_t is not None else (None, None)
+        v = _IswtLevel.apply(lows, highs, taps[4], taps[5], dilation, 1.0, *zt)
+    else:
+        v = _level_inv(lows, highs, taps[4], taps[5], dilation, 1.0)
+    v = v.reshape(4, b, h, w, dz).permute(0, 1, 4, 2, 3).reshape(4, b * dz, h, w)  # plane 2 [axis -2 high] + [axis -1 high]
+    quad = (v[0], v[2], v[1], v[3])  # cA, cH (axis -2 high), cV (axis -1 high), cD as the 2-D level takes them
+    if tap_t is not None:
+        y = _composed2_inv(quad, taps[:4], dilation, scale, tuple(tap_t[:4]))
+    elif diff:
+        y = _Iswt2Level.apply(*quad, tuple(taps[:4]), dilation, scale)
+    else:
+        y = _level2_inv(quad, taps[:4], dilation, scale)
+    return y.reshape(b, dz, h, w)
+
+
+def _vols(t: torch.Tensor) -> torch.Tensor:
+    return _engine._unit_last(t)  # [B, Dz, H, W] with contiguous samples (volume / slice / row strides free)
+
+
+def _taps6_array(taps: Taps6):
+    return _dbl_p6(*[ctypes.cast(_engine._taps_array(t), _dbl_p) for t in taps])
+
+
+def _level3_fwd(x: torch.Tensor, taps: Taps6, dilation: int, scale: float, composed: bool = False) -> torch.Tensor:
+    """x [B, Dz, H, W] -> level buffer [B, 8, Dz, H, W] (planes aaa .. ddd): the fused launch where it exists, else (or with
+    ``composed``) the composed route.  No autograd."""
+    _engine._require_gpu(x)
+    b, dz, h, w = x.shape
+    flen = len(taps[0])
+    taps = _merged6(taps, dilation, dz, h, w)
+    if composed or not _fused3("fwd", x.dtype, flen, b, dz, h, w, dilation):
+        with torch.no_grad():
+            return _composed3_fwd(x.detach(), taps, dilation, scale)
+    x = _vols(x)
+    buf = torch.empty((b, 8, dz, h, w), dtype=x.dtype, device=x.device)
+    if buf.numel() == 0:
+        return buf
+    plane = dz * h * w * buf.element_size()
+    _engine._enqueue(x, _swt3_entries().mifwt_swt3_fwd, _engine._DTYPE_IDS[x.dtype], flen, b, dz, h, w, dilation, x.data_ptr(),
+                     x.stride(0), x.stride(1), x.stride(2), _vp8(*[buf.data_ptr() + q * plane for q in range(8)]),
+                     _i64x8(*[8 * dz * h * w] * 8), _i64x8(*[h * w] * 8), _i64x8(*[w] * 8), _taps6_array(taps), scale)
+    return buf
+
+
+def _level3_inv(bands: Sequence[torch.Tensor], taps: Taps6, dilation: int, scale: float, composed: bool = False) -> torch.Tensor:
+    """(aaa, .., ddd), each [B, Dz, H, W] with any volume / slice / row strides -> y [B, Dz, H, W].  No autograd."""
+    _engine._require_gpu(bands[0])
+    b, dz, h, w = bands[0].shape
+    flen = len(taps[0])
+    taps = _merged6(taps, dilation, dz, h, w)
+    if composed or not _fused3("inv", bands[0].dtype, flen, b, dz, h, w, dilation):
+        with torch.no_grad():
+            return _composed3_inv([t.detach() for t in bands], taps, dilation, scale)
+    bands = [_vols(t) for t in bands]
+    y = torch.empty((b, dz, h, w), dtype=bands[0].dtype, device=bands[0].device)
+    if y.numel() == 0:
+        return y
+    _engine._enqueue(y, _swt3_entries().mifwt_swt3_inv, _engine._DTYPE_IDS[y.dtype], flen, b, dz, h, w, dilation,
+                     _vp8(*[t.data_ptr() for t in bands]), _i64x8(*[t.stride(0) for t in bands]), _i64x8(*[t.stride(1) for t in bands]),
+                     _i64x8(*[t.stride(2) for t in bands]), y.data_ptr(), dz * h * w, h * w, w, _taps6_array(taps), scale)
+    return y
+
+
+def swt3_plan(dtype: torch.dtype, flen: int, inverse: bool, b: int, dz: int, h: int, w: int, dilation: int) -> Optional[dict]:
+    """The work split ``mifwt_swt3_plan`` reports for a fused 3-D level (host code, no launch), or None where there is no fused launch."""
+    out = (ctypes.c_int * SWT3_PLAN_INTS)()
+    n = _swt3_entries().mifwt_swt3_plan(_engine._DTYPE_IDS[dtype], flen, int(inverse), b, dz, h, w, dilation, out, SWT3_PLAN_INTS)
+    if n != SWT3_PLAN_INTS:
+        return None
+    names = ("slice_residues", "row_residues", "segments", "segment_length", "row_tiles", "strips", "RT", "RW", "E", "lds_bytes", "threads")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+class _Swt3Level(torch.autograd.Function):
+    """One 3-D analysis level with host taps and a free scale.  Its transpose is the synthesis level with all six filters reversed and
+    the same scale (and vice versa), so each Function's backward is the other Function: data gradients of any order."""
+
+    @staticmethod
+    def forward(ctx, x, taps, dilation, scale):
+        ctx.meta = (taps, dilation, scale)
+        return _level3_fwd(x, taps, dilation, scale)
+
+    @staticmethod
+    def backward(ctx, g_buf):
+        taps, dilation, scale = ctx.meta
+        return _Iswt3Level.apply(*(g_buf[:, q] for q in range(8)), _rev4(taps), dilation, scale), None, None, None
+
+
+class _Iswt3Level(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, c0, c1, c2, c3, c4, c5, c6, c7, taps, dilation, scale):
+        ctx.meta = (taps, dilation, scale)
+        return _level3_inv((c0, c1, c2, c3, c4, c5, c6, c7), taps, dilation, scale)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        taps, dilation, scale = ctx.meta
+        g = _Swt3Level.apply(g_y, _rev4(taps), dilation, scale)
+        return (*(g[:, q] for q in range(8)), None, None, None)
+
+
+def swt3(data: torch.Tensor, wavelet: Union[Wavelet, str], level: Optional[int] = None, *,
+         axes: Tuple[int, int, int] = (-3, -2, -1)) -> WaveletCoeffNd:
+    """Multi-level 3-D stationary transform over ``axes``.  Returns ``[cA_n, {"aad": .., "ada": .., "add": .., "daa": .., "dad": ..,
+    "dda": .., "ddd": ..}_n, ..., {...}_1]``, every tensor of the input's shape: the container of ``wavedec3``, the first letter of a
+    key belonging to ``axes[0]`` (``a`` low-pass, ``d`` high-pass).  By construction this is ``pywt.swtn(..., trim_approx=True,
+    norm=False)`` over the three axes.
+
+    A level is the level of :func:`swt` (periodic, dilation ``2^level index``, scale 1) along each of the three axes.  ``level=None``
+    means the minimum of ``swt_max_level`` over the three extents — odd extents give ``[data]``; as in :func:`swt` no level is refused,
+    the periodic index map wraps as often as needed.  Only float32 and float64 are accepted: float16 raises ``ValueError("Input dtype
+    ... not supported")`` even inside ``half_storage()`` (the fused kernels have no float16 form).  Differentiable w.r.t. the data to
+    any order; a learnable (tensor-valued) filter bank runs on the composed route and has tap gradients up to second order."""
+    axes = _fwt._ensure_axes(axes, 3)
+    layout = _fwt._Layout(data, 3, axes)
+    _check_dtype2(data)
+    x = layout.fold(data)
+    dec_lo, dec_hi, _, _ = host_taps(wavelet)
+    tap_t = _fwt._tap_tensors(wavelet)
+    if level is None:
+        level = min(swt_max_level(n) for n in x.shape[-3:])
+    taps = (tuple(dec_lo), tuple(dec_hi)) * 3
+    out: list = []
+    cur = x
+    for lvl in range(level):
+        _engine._require_gpu(cur)
+        if tap_t is not None:
+            buf = _composed3_fwd(cur, taps, 2 ** lvl, 1.0, (tap_t[0], tap_t[1]) * 3)
+        elif torch.is_grad_enabled() and cur.requires_grad:
+            buf = _Swt3Level.apply(cur, taps, 2 ** lvl, 1.0)
+        else:
+            buf = _level3_fwd(cur, taps, 2 ** lvl, 1.0)
+        out.append({key: layout.unfold(buf[:, q + 1]) for q, key in enumerate(_KEYS3)})
+        cur = buf[:, 0]
+    out.append(layout.unfold(cur))
+    out.reverse()
+    return out
+
+
+def iswt3(coeffs: WaveletCoeffNd, wavelet: Union[Wavelet, str], *, axes: Tuple[int, int, int] = (-3, -2, -1)) -> torch.Tensor:
+    """Inverse of :func:`swt3` (by construction ``pywt.iswtn`` of coefficients with ``trim_approx=True, norm=False``).  Per level the
+    synthesis level of :func:`iswt` (scale 1/2 per axis, 1/8 in all) along ``axes[2]``, ``axes[1]`` and ``axes[0]``: a linear map of ANY
+    coefficient set, not only of images of ``swt3``.  float32 / float64 only, as :func:`swt3`."""
+    coeffs = list(coeffs)
+    if not coeffs or not isinstance(coeffs[0], torch.Tensor):
+        raise ValueError("First element of coeffs must be the approximation coefficient tensor.")
+    axes = _fwt._ensure_axes(axes, 3)
+    layout = _fwt._Layout(coeffs[0], 3, axes)
+    flat = [coeffs[0]]
+    for c in coeffs[1:]:
+        if not isinstance(c, dict) or set(c.keys()) != set(_KEYS3):
+            raise ValueError(f"Unexpected detail coefficient type: {type(c)}. Detail coefficients must be a dict of tensors with the "
+                             f"seven keys {', '.join(_KEYS3)} as returned by swt3.")
+        for key in _KEYS3:
+            if not isinstance(c[key], torch.Tensor):
+                raise ValueError(f"Unexpected input type {type(c[key])}")
+            flat.append(c[key])
+    _fwt._check_same_device_dtype(flat)
+    _check_dtype2(coeffs[0])
+    _, _, rec_lo, rec_hi = host_taps(wavelet)
+    tap_t = _fwt._tap_tensors(wavelet)
+    taps = (tuple(rec_lo), tuple(rec_hi)) * 3
+    cur = layout.fold(coeffs[0])
+    details = [tuple(layout.fold(c[key]) for key in _KEYS3) for c in coeffs[1:]]
+    for det in details:
+        for t in det:
+            if t.shape != cur.shape:
+                raise ValueError(f"detail coefficients of shape {tuple(t.shape)} do not match the approximation of shape "
+                                 f"{tuple(cur.shape)} (folded to [batch, D, H, W])")
+    for pos, det in enumerate(details):
+        dilation = 2 ** (len(details) - pos - 1)
+        bands = (cur, *det)
+        _engine._require_gpu(cur)
+        if tap_t is not None:
+            cur = _composed3_inv(bands, taps, dilation, 0.125, (tap_t[2], tap_t[3]) * 3)
+        elif torch.is_grad_enabled() and any(t.requires_grad for t in bands):
+            cur = _Iswt3Level.apply(*bands, taps, dilation, 0.125)
+        else:
+            cur = _level3_inv(bands, taps, dilation, 0.125)
     return layout.unfold(cur)
