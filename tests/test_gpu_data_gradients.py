@@ -2,7 +2,8 @@
 w.r.t. the coefficients — element by element against the differentiable float64 CPU reference (oracle/torch_autograd_ref.py, pinned to
 the reference library's gradient goldens by tests/test_torch_autograd_ref.py), at the shapes where the routed kernels run.
 
-One case = one differentiable call.  Compared tensor by tensor with ``R`` on the same inputs (quantised to the case's dtype, then
+One case = one differentiable call through the harness of tests/_grad_ref.py (``Harness.run``, shared with
+tests/test_gpu_independent_banks.py).  Compared tensor by tensor with ``R`` on the same inputs (quantised to the case's dtype, then
 widened): the coefficients of ``fn(x)``; d/dx of ``sum_i <w_i, c_i>``; the reconstruction ``rec(leaves)``; the gradients of
 ``<v, rec(leaves)>`` w.r.t. every leaf.  ``w_i`` and ``v`` are seeded GAUSSIAN tensors (tests/_grad_ref.py says why).  Per tensor: shape
 and dtype, the norm-wise error, the max-abs error over the largest reference value and — d/dx only — the norm-wise error of the BORDER
@@ -32,9 +33,6 @@ Shapes moved from the issue's list: 1 x 40 x 33 x 36 db3 runs in float64 (float3
 serves float64 volumes below the walking kernels' threshold); the slab form of kernel 24 runs on 2 x 40 x 44 x 100 db4 under
 MIFWT_OPT_TILE_MODE 4 (the default route takes it from 4 x 100^3 on).
 """
-import contextlib
-from collections import namedtuple
-
 import numpy as np
 import pytest
 import torch
@@ -52,7 +50,7 @@ F32_REF = {"norm": 5.82e-07, "maxabs": 1.56e-06, "border": 4.09e-07}
 F32_BOUNDS = {m: 10 * v for m, v in F32_REF.items()}
 F64_BOUNDS = {m: 1e-11 * F32_REF[m] / F32_REF["norm"] for m in F32_REF}
 BOUNDS = {f32: F32_BOUNDS, f64: F64_BOUNDS}
-LEGS = ("fwd", "inv", "fwd_adj", "inv_adj")
+LEGS = D.LEGS
 STRIPS = 2097152  # MIFWT_OPT_DEBUG routing bit: kernel 24 keeps its strip form for eight / ten taps
 FN2 = ("wavedec2", "fswavedec2")
 MODES5 = ("zero", "constant", "reflect", "periodic", "symmetric")
@@ -65,142 +63,20 @@ TILE_SHAPES = [((3, 61, 128), "db2"), ((2, 64, 70), "db4"), ((1, 131, 67), "db3"
 ROWS = [((3, 5001), "db4", 5), ((2, 40000), "db5", 8), ((40, 1000), "db2", 4), ((2, 4097), "haar", 10)]
 BRICK_SHAPES = [((2, 24, 26, 31), "db2"), ((2, 18, 20, 19), "haar")]
 
-Case = namedtuple("Case", "fn shape wavelet mode level dtype axes seed", defaults=(None, 0))
+Case = D.Case
 
-REACHED = set()  # (leg, kernel id) and ("border", "line" | "sample" | "1d" | "3d") of the whole module
-WORST = {f32: {}, f64: {}}  # worst error per dtype and measure
-_REFS = {}  # case -> (inputs, float64 results): computed once per case, shared by its route variants
-F32_CASES = []  # every float32 case that ran with Gaussian cotangents: f32_cases() must list them all
+# the harness of tests/_grad_ref.py with this module's bounds; its state under the names the tests below (and the CPU companion) use
+H = D.Harness(BOUNDS)
+REACHED = H.reached  # (leg, kernel id) and ("border", "line" | "sample" | "1d" | "3d") of the whole module
+WORST = H.worst  # worst error per dtype and measure
+_REFS = H.refs  # case -> (inputs, float64 results): computed once per case, shared by its route variants
+F32_CASES = H.f32_cases  # every float32 case that ran with Gaussian cotangents: f32_cases() must list them all
+run, check, reference, recording = H.run, H.check, H.reference, H.recording
+options, border_kernel, ids = D.options, D.border_kernel, D.ids
 
 
 def dev():
     return torch.device("cuda:0")
-
-
-def reference(case):
-    if case not in _REFS:
-        inp = D.inputs(case.fn, case.shape, case.wavelet, case.mode, case.level, case.dtype, case.axes, case.seed)
-        _REFS[case] = (inp, D.chain(case.fn, case.wavelet, inp))
-        if len(_REFS) > 6:
-            _REFS.pop(next(iter(_REFS)))
-    return _REFS[case]
-
-
-@contextlib.contextmanager
-def options(opts):
-    try:
-        for k, v in opts:
-            _engine.set_option(k, v)
-        yield
-    finally:
-        for k, _ in opts:
-            _engine.set_option(k, 0)
-
-
-@contextlib.contextmanager
-def recording(into, leg):
-    _engine.level_events = []
-    try:
-        yield
-        torch.cuda.synchronize()
-        into[leg] = [(e[0], e[1], e[2]) for e in _engine.level_events]
-    finally:
-        _engine.level_events = None
-
-
-def border_kernel(ndim, flen, mode, ext, debug):
-    """Which border kernel an analysis adjoint of this geometry runs after its synthesis launch (adjoint_border_supported / border2_fits of
-    csrc/mifwt_adjoint_border.hip), or None."""
-    if mode == "zero" or (debug & 1024) or flen % 2 or flen > 32 or any(n < 2 * (flen + 1) for n in ext):
-        return None
-    if ndim == 2:
-        return "line" if flen >= 8 and not (debug & 4096) else "sample"
-    return "1d" if ndim == 1 else "3d"
-
-
-def check(got, want, dtype, what, mask=None, rows=None):
-    """Shape, dtype and the three measures of one tensor against the bounds; the figures go into WORST before anything is asserted."""
-    assert got.dtype == dtype, (what, got.dtype)
-    got = got.detach().double().cpu().numpy()
-    want = want.double().numpy()
-    if rows is None:
-        assert got.shape == want.shape, (what, got.shape, want.shape)
-        m = D.measures(got, want, mask)
-    else:
-        assert got.shape == (rows,) + want.shape[1:], (what, got.shape, want.shape)
-        m = D.rowwise_measures(got, want, want.shape[0], mask)
-    for k, v in m.items():
-        WORST[dtype][k] = max(WORST[dtype].get(k, 0.0), v)
-    for k, v in m.items():
-        assert v < BOUNDS[dtype][k], (what, k, v, BOUNDS[dtype][k])
-    return m
-
-
-def run(case, opts=(), create_graph=False, expect=None, generic=(), layout=None, loss="gauss", rows=None):
-    """One case on the GPU against its reference.  ``expect``: leg -> kernel ids that must all appear on it; ``generic``: legs that may
-    reach the generic passes; ``layout``: "transposed" hands x over as a transposed view; ``loss``: "gauss", "sum" (sum of c.sum(): the
-    backward gets expanded stride-0 cotangents) or an index (that band alone: the other cotangents arrive as zeros); ``rows``: the batch
-    of the GPU run, built from the case's (fewer) distinct rows."""
-    inp, want = reference(case)
-    if loss != "gauss":  # (another cotangent of the analysis: its own reference chain, the inputs stay)
-        inp = dict(inp)
-        inp["w"] = [torch.ones_like(w) if loss == "sum" else (w if i == loss else torch.zeros_like(w)) for i, w in enumerate(inp["w"])]
-        want = D.chain(case.fn, case.wavelet, inp)
-    elif case.dtype == f32:
-        if case not in F32_CASES:
-            F32_CASES.append(case)
-    fn, rec = getattr(ptwt_amd, case.fn), getattr(ptwt_amd, D.FNS[case.fn][0])
-    up = (lambda t: t.to(dev())) if rows is None else (lambda t: D.tile_rows(t, rows).to(dev()))
-    what = tuple(case) + (tuple(opts), create_graph, layout, loss, rows)
-    debug = dict(opts).get(_engine.OPT_DEBUG, 0)
-    ev = {}
-    with options(opts):
-        x = up(inp["x"])
-        if layout == "transposed":
-            x = x.transpose(-1, -2).contiguous().transpose(-1, -2)
-            assert not x.is_contiguous()
-        x.requires_grad_(True)
-        with recording(ev, "fwd"):
-            coeffs = fn(x, case.wavelet, **inp["kw"], **inp["akw"])
-        fl = D.flat(coeffs)
-        assert len(fl) == len(want["coeffs"]), what
-        if loss == "sum":
-            total = sum(c.sum() for c in fl)
-        elif loss == "gauss":
-            total = sum((up(w) * c).sum() for w, c in zip(inp["w"], fl))
-        else:
-            total = (up(inp["w"][loss]) * fl[loss]).sum()
-        with recording(ev, "fwd_adj"):
-            (gx,) = torch.autograd.grad(total, x, create_graph=create_graph)
-        leaves = [up(t).requires_grad_(True) for t in inp["leaves"]]
-        with recording(ev, "inv"):
-            y = rec(D.rebuild(inp["template"], leaves), case.wavelet, **inp["akw"])
-        with recording(ev, "inv_adj"):
-            gl = torch.autograd.grad((up(inp["v"]) * y).sum(), leaves, create_graph=create_graph)
-    for i, (a, b) in enumerate(zip(fl, want["coeffs"])):
-        check(a, b, case.dtype, what + ("coefficient", i), rows=rows)
-    axes = D.norm_axes(case.fn, len(case.shape), case.axes)
-    mask = D.border_mask(case.shape[1:] if rows else case.shape, [a - 1 for a in axes] if rows else axes, D.filt_len(case.wavelet))
-    check(gx, want["gx"], case.dtype, what + ("d/dx",), mask=mask, rows=rows)
-    check(y, want["rec"], case.dtype, what + ("reconstruction",), rows=rows)
-    for i, (a, b) in enumerate(zip(gl, want["gleaves"])):
-        check(a, b, case.dtype, what + ("d/dleaf", i), rows=rows)
-    # routes: after the numbers, so that a moved route does not hide a wrong gradient
-    kids = {leg: {k for _, k, _ in ev[leg]} for leg in LEGS}
-    for leg in LEGS:
-        REACHED.update((leg, k) for k in kids[leg])
-        assert 0 not in kids[leg] or leg in generic, (what, leg, "generic passes", ev[leg])
-        assert set((expect or {}).get(leg, ())) <= kids[leg], (what, leg, "expected", expect[leg], "ran", ev[leg])
-    nd, flen = D.FNS[case.fn][1], D.filt_len(case.wavelet)
-    for eng_leg, _, ext in ev["fwd_adj"]:
-        b = border_kernel(nd, flen, case.mode, ext, debug) if eng_leg == "fwd_adj" else None
-        if b:
-            REACHED.add(("border", b))
-    return ev, kids
-
-
-def ids(ev, leg):
-    return [(e, k) for e, k, _ in ev[leg]]
 
 
 # ---- 2-D float32: the streaming multi-level kernels 16 / 22 -----------------------------------------------------------------------------
