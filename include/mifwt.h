@@ -463,6 +463,43 @@ int mifwt_bwt_tree_fwd(int dtype, int filt_len, int64_t rows, int64_t n, int64_t
 int mifwt_bwt_tree_inv(int dtype, int filt_len, int64_t rows, int64_t n, int nlevels, const void* leaves, void* const* levels,
                        const double* lo, const double* hi, const mifwt_bwt_tables* tables, void* stream);
 
+/* PERIODIZED levels — PyWavelets' mode="periodization" (pywt.dwt / pywt.idwt and their N-D forms; the reference has no such mode): an
+ * axis of N samples gives ceil(N / 2) coefficients per band, any N >= 1, exactly orthogonal for orthogonal wavelets.  Per axis, L even,
+ * taps in PyWavelets order:
+ *     extension   N~ = N + (N mod 2);  x~[i] = x[min(i, N - 1)] for 0 <= i < N~ (an odd extent repeats its last sample), then periodic
+ *                 with period N~, any number of wraps (N = 1 and N < L are valid)
+ *     analysis    M = N~ / 2;  cA[k] = sum_j dec_lo[j] x~[(2 k + L/2 - j) mod N~],  cD likewise with dec_hi,  0 <= k < M
+ *     synthesis   y[(2 k + t - L/2 + 1) mod 2 M] += rec_lo[t] cA[k] + rec_hi[t] cD[k],  0 <= k < M, 0 <= t < L  (2 M samples, one more than
+ *                 an odd input had, exactly as pywt.idwt)
+ * N-D: the 1-D level per transformed axis, separably; band order as everywhere (bit (ndim-1-a) set <=> high-pass along axis a).
+ *   desc      as for mifwt_bwt_fwd: sig_extent the REAL extent (may be odd), coef_extent = ceil(sig_extent / 2) per axis (anything else:
+ *             MIFWT_ERR_BADARG); `mode` is ignored.  Synthesis accepts sig_extent in {2 M, 2 M - 1} and writes only those samples.
+ *   lo / hi   HOST taps, PyWavelets order: dec_lo / dec_hi for mifwt_per_fwd, rec_lo / rec_hi for mifwt_per_inv
+ * Adjoints need no entry points of their own: the adjoint of an analysis level is mifwt_per_inv with rec[t] := dec[L-1-t] over N~ samples,
+ * after which the caller adds the gradient of the virtual sample N~ - 1 of an odd extent to sample N - 1; the adjoint of a synthesis level
+ * is mifwt_per_fwd with dec[j] := rec[L-1-j].
+ * Fused kernels (ids 38 / 39, csrc/mifwt_per.hip): f32 / f64, even L from 2 to 20, ndim 1 or 2, unit innermost strides, any extent >= 1: one
+ * launch per level, the plane read once and the bands written once.  mifwt_per_supported / mifwt_per_kernel_id are decided on the host:
+ * 1 / the kernel id where the fused kernels serve the level, 0 / MIFWT_ERR_UNSUPPORTED where they do not (mifwt_per_fwd / _inv then
+ * launch nothing and return MIFWT_ERR_UNSUPPORTED), MIFWT_ERR_BADARG for inconsistent arguments.
+ * mifwt_per_axis_fwd / _inv: ONE axis of a level through a run-time tap loop (ids 40 / 41): arrays [outer, n, inner] with (outer, axis,
+ * inner) strides in elements, even L <= MIFWT_MAX_FILT, f32 / f64, any n >= 1 (n_out in {2 M, 2 M - 1} for M coefficients). */
+#define MIFWT_KID_PER_FWD 38       /* fused level, ndim 1 or 2 */
+#define MIFWT_KID_PER_INV 39
+#define MIFWT_KID_PER_AXIS_FWD 40  /* one axis, any strides, run-time tap loop */
+#define MIFWT_KID_PER_AXIS_INV 41
+int mifwt_per_supported(const mifwt_level_desc* desc, int direction);
+int mifwt_per_kernel_id(const mifwt_level_desc* desc, int direction);
+int mifwt_per_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* lo, const double* hi,
+                  void* stream);
+int mifwt_per_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* lo, const double* hi,
+                  void* stream);
+int mifwt_per_axis_fwd(int dtype, int filt_len, int64_t outer, int64_t n, int64_t inner, const void* x, const int64_t* x_strides, void* lo_out,
+                       const int64_t* lo_strides, void* hi_out, const int64_t* hi_strides, const double* lo, const double* hi, void* stream);
+int mifwt_per_axis_inv(int dtype, int filt_len, int64_t outer, int64_t n_out, int64_t inner, const void* lo_in, const int64_t* lo_strides,
+                       const void* hi_in, const int64_t* hi_strides, void* y, const int64_t* y_strides, const double* lo, const double* hi,
+                       void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -520,7 +557,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   30 / 31  fused 3-D boundary-wavelet analysis / synthesis level, LDS bricks (mifwt_bwt3_fwd / mifwt_bwt3_inv; f32 / f64, even L <= 8;
  *          answered by mifwt_bwt3_kernel_id)
  *   32 / 33  a subtree (two or more levels) of a 1-D boundary-wavelet packet tree per launch, analysis / synthesis, one row per workgroup
- *          (mifwt_bwt_tree_fwd / mifwt_bwt_tree_inv; f32 / f64, even L <= 20; answered by mifwt_bwt_tree_levels) */
+ *          (mifwt_bwt_tree_fwd / mifwt_bwt_tree_inv; f32 / f64, even L <= 20; answered by mifwt_bwt_tree_levels)
+ *   38 / 39  fused periodized analysis / synthesis level, 1-D and 2-D (mifwt_per_fwd / mifwt_per_inv; answered by mifwt_per_kernel_id)
+ *   40 / 41  one axis of a periodized level through a run-time tap loop (mifwt_per_axis_fwd / mifwt_per_axis_inv) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).
@@ -553,8 +592,8 @@ int mifwt_set_option(int key, int value);
 int mifwt_pyr_profile_buffer(void* device_buffer);
 
 /* Diagnostic: how many launches of a kernel VARIANT this process has enqueued — variants that share a kernel id (what the tests use to
- * pin "this code path ran"; `variant` out of range: 0).  Values below 16 are variants; the 2-D and 3-D stationary kernels, which have no
- * variants, are counted under their kernel ids. */
+ * pin "this code path ran"; `variant` out of range: 0).  Values below 16 are variants; the 2-D and 3-D stationary kernels and the
+ * periodized kernels (MIFWT_KID_PER_*, 38 .. 41), which have no variants, are counted under their kernel ids. */
 #define MIFWT_VARIANT_FWD_MFMA_WALK 0 /* id 11: the analysis kernel that walks down column panels */
 #define MIFWT_VARIANT_FWD_MFMA_TILE 1 /* id 11: the tile-at-a-time analysis kernel of round 2 (MIFWT_OPT_MFMA_MODE 3) */
 #define MIFWT_VARIANT_FWD_PYR_ST16 2  /* id 16: 16-byte stores after a lane-pair exchange (planes with 16-byte aligned rows) */

@@ -133,6 +133,18 @@ _ENTRIES: dict = {
     "mifwt_dwt1_inv_outer": (_c, [_c] + [_i64] * 4 + [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _c, _dbl_p, _dbl_p, _vp, _vp, _vp]),
     "mifwt_dwt1_fwd_outer": (_c, [_c, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _c, _c, _dbl_p, _dbl_p, _vp, _vp, _vp]),
 }
+# The periodized levels (_per.py; include/mifwt.h, mifwt_per_*).  Bound by :func:`private_entries` on function objects of their own,
+# not on the shared library object: what is bound there is the surface tests/golden/engine_calls.json records call by call, and that
+# fixture is about the padded, stationary and boundary-wavelet paths.  None of them may be missing from a build.
+PER_ENTRIES: dict = {
+    "mifwt_per_supported": (_c, [_desc_p, _c]),
+    "mifwt_per_kernel_id": (_c, [_desc_p, _c]),
+    "mifwt_per_fwd": (_c, [_desc_p, _vp, _vp, _vpp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_per_inv": (_c, [_desc_p, _vp, _vpp, _vp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_per_axis_fwd": (_c, [_c, _c, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _vp]),
+    "mifwt_per_axis_inv": (_c, [_c, _c, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _vp]),
+}
+
 _MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
                    "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
 _abi_mismatch = False
@@ -151,6 +163,21 @@ def register_entries(table: dict) -> None:
     _ENTRIES.update(table)
     if _lib is not None:
         _bind(_lib, table)
+
+
+class _Entries:
+    """Function objects of a table of entry points, as attributes."""
+
+    def __init__(self, lib, table: dict):
+        for name, (restype, argtypes) in table.items():
+            fn = lib[name]  # (item access: a fresh function object that the library object does not keep; a missing symbol raises)
+            fn.restype, fn.argtypes = restype, argtypes
+            setattr(self, name, fn)
+
+
+def private_entries(table: dict) -> _Entries:
+    """The entry points of ``table`` (name -> (restype, argtypes)) bound on function objects of the caller's own."""
+    return _Entries(load_library(), table)
 
 
 def load_library() -> ctypes.CDLL:

@@ -820,6 +820,8 @@ def _check_pad_levels(extents: Sequence[int], flen: int, mode, level: int) -> No
 
 def analysis(data: torch.Tensor, wavelet, mode, level: Optional[int], axes: AxisHint, ndim: int):
     """Multi-level analysis.  Returns ``(layout, approx [B,*M], [buffer [B,2^n,*M] per level, coarsest first])``."""
+    if isinstance(mode, str) and mode == PERIODIZATION:
+        return _analysis_per(data, wavelet, level, axes, ndim)
     axes = _ensure_axes(axes, ndim)
     layout = _Layout(data, ndim, axes)
     x = layout.fold(data)
@@ -1001,8 +1003,13 @@ def _pyramid_route(cur: torch.Tensor, folded, exts, flen: int, separable: bool):
 
 
 def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, axes: AxisHint, ndim: int,
-              separable: bool) -> torch.Tensor:
-    """Multi-level synthesis.  ``levels``: per level (coarsest first) the 2^n-1 detail tensors in band order."""
+              separable: bool, mode=None) -> torch.Tensor:
+    """Multi-level synthesis.  ``levels``: per level (coarsest first) the 2^n-1 detail tensors in band order.  ``mode``: "periodization"
+    selects the periodized synthesis; the padded synthesis does not depend on its mode, which is only checked."""
+    if isinstance(mode, str) and mode == PERIODIZATION:
+        return _synthesis_per(approx, levels, wavelet, axes, ndim, separable)
+    if mode is not None:
+        _mode_id(mode)
     axes = _ensure_axes(axes, ndim)
     layout = _Layout(approx, ndim, axes)
     flat = [approx] + [t for lvl in levels for t in lvl]
@@ -1124,6 +1131,81 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
         else:
             cur = eng.synthesis(cur, det, rec_lo, rec_hi, exts[pos])
         pos += 1
+    return layout.unfold(cur)
+
+
+# ------------------------------------------------------------------------------------------ periodization
+# PyWavelets' mode="periodization" (include/mifwt.h, _per.py): ceil(n / 2) coefficients per axis and level, any extent, one level
+# call per trip.  Not one of _engine.MODE_IDS — the Matrix* classes consult those for their odd_coeff_padding_mode — so both drivers
+# branch on the string before _mode_id.
+PERIODIZATION = "periodization"
+
+
+def _per_taps(wavelet, proto: torch.Tensor):
+    """The refusals of the periodized mode that need no device, and the bank as host floats (tensor taps are read once)."""
+    if proto.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"Input dtype {proto.dtype} not supported")
+    if _tap_tensors(wavelet) is not None:
+        raise NotImplementedError("mode='periodization' does not take a learnable filter bank (taps that require grad)")
+    bank = wavelet if isinstance(wavelet, tuple) else getattr(wavelet, "filter_bank", ())
+    tensor_bank = not isinstance(wavelet, str) and len(bank) == 4 and all(isinstance(t, torch.Tensor) for t in bank)
+    if tensor_bank and (_wavelets._device_taps_mode == "always" or (proto.is_cuda and device_bank(wavelet, proto.device) is not None)):
+        raise NotImplementedError("mode='periodization' does not take device-resident taps (set_device_taps): its kernels read host taps")
+    taps = host_taps(wavelet)
+    if len(taps[0]) != len(taps[2]) or len(taps[0]) % 2:
+        raise ValueError("mode='periodization' needs dec and rec filters of one even length")
+    return taps
+
+
+def _analysis_per(data: torch.Tensor, wavelet, level: Optional[int], axes: AxisHint, ndim: int):
+    from . import _per
+
+    axes = _ensure_axes(axes, ndim)
+    layout = _Layout(data, ndim, axes)
+    dec_lo, dec_hi, _, _ = _per_taps(wavelet, data)
+    x = layout.fold(data)
+    if level is None:
+        level = dwtn_max_level(x.shape[1:], len(dec_lo))
+    elif level < 0:  # (pywt.wavedec: "Level value must be >= 0"; level 0 returns the input as the approximation, as in every mode)
+        raise ValueError(f"Level value of {level} is too low. Minimum level is 0.")
+    _engine._require_gpu(x)
+    bufs: list = []  # coarsest level first
+    cur = x
+    for _ in range(level):
+        buf = _per.fwd(cur, dec_lo, dec_hi)
+        bufs.insert(0, buf)
+        cur = buf[:, 0]
+    return layout, cur, bufs
+
+
+def _synthesis_per(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, axes: AxisHint, ndim: int, separable: bool) -> torch.Tensor:
+    from . import _per
+
+    axes = _ensure_axes(axes, ndim)
+    layout = _Layout(approx, ndim, axes)
+    flat = [approx] + [t for lvl in levels for t in lvl]
+    for t in flat:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"Unexpected input type {type(t)}")
+    _check_same_device_dtype(flat)
+    _, _, rec_lo, rec_hi = _per_taps(wavelet, approx)
+    cur = layout.fold(approx)
+    _engine._require_gpu(cur)
+    folded = [[layout.fold(t) for t in lvl] for lvl in levels]
+    for pos, det in enumerate(folded):
+        if separable:  # (the separable containers crop the running approximation to the detail shape, as in the padded synthesis)
+            cur = cur[tuple(slice(0, s_) for s_ in det[0].shape)]
+        for t in det:
+            if tuple(t.shape) != tuple(cur.shape):
+                if ndim == 1:
+                    raise RuntimeError("stack expects each tensor to be equal size")
+                raise ValueError("All coefficients on each level must have the same shape")
+        out_ext = [2 * int(m) for m in cur.shape[1:]]
+        if not separable and pos + 1 < len(folded):
+            # an intermediate result loses its last sample along an axis where it is one longer than the next level's details
+            nxt = folded[pos + 1][0].shape
+            out_ext = [n - _adjust_trim(n, int(nxt[1 + a])) for a, n in enumerate(out_ext)]
+        cur = _per.inv([cur, *det], rec_lo, rec_hi, out_ext)
     return layout.unfold(cur)
 
 

@@ -11,6 +11,7 @@ import torch
 
 __all__ = [
     "BoundaryMode",
+    "ExtendedBoundaryMode",
     "SUPPORTED_DTYPES",
     "set_half_storage",
     "half_storage",
@@ -61,6 +62,9 @@ def supported_dtypes():
 #: boundary rules (src/ptwt/constants.py:85): zero | constant (edge replicate) | reflect (whole-sample
 #: mirror) | periodic | symmetric (half-sample mirror)
 BoundaryMode = Literal["constant", "zero", "reflect", "periodic", "symmetric"]
+#: the padded modes and PyWavelets' ``"periodization"``: ``ceil(N / 2)`` coefficients per axis and level, exactly orthogonal for
+#: orthogonal wavelets (an engine extension; the ``Matrix*`` classes keep taking :data:`BoundaryMode` only)
+ExtendedBoundaryMode = Union[BoundaryMode, Literal["periodization"]]
 
 
 class Wavelet(Protocol):

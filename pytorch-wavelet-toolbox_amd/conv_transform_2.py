@@ -6,12 +6,12 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _fwt
-from .constants import BoundaryMode, Wavelet, WaveletCoeff2d
+from .constants import ExtendedBoundaryMode, Wavelet, WaveletCoeff2d
 
 __all__ = ["wavedec2", "waverec2"]
 
 
-def wavedec2(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: BoundaryMode = "reflect",
+def wavedec2(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: ExtendedBoundaryMode = "reflect",
              level: Optional[int] = None, axes: Tuple[int, int] = (-2, -1)) -> WaveletCoeff2d:
     """Multi-level 2-D analysis; returns ``(cA_n, (H,V,D)_n, ..., (H,V,D)_1)``.
 
@@ -23,8 +23,10 @@ def wavedec2(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: Boundary
     return _fwt.pack_2d(layout, approx, bufs)
 
 
-def waverec2(coeffs: WaveletCoeff2d, wavelet: Union[Wavelet, str], *, axes: _fwt.AxisHint = None) -> torch.Tensor:
-    """Inverse of :func:`wavedec2` (src/ptwt/conv_transform_2.py:160-253)."""
+def waverec2(coeffs: WaveletCoeff2d, wavelet: Union[Wavelet, str], *, axes: _fwt.AxisHint = None,
+             mode: Optional[ExtendedBoundaryMode] = None) -> torch.Tensor:
+    """Inverse of :func:`wavedec2` (src/ptwt/conv_transform_2.py:160-253).  ``mode``: ``"periodization"`` inverts a periodized
+    decomposition; None or a padded mode is the padded synthesis, which does not depend on the mode."""
     if len(coeffs) == 0 or not isinstance(coeffs[0], torch.Tensor):
         raise ValueError("First element of coeffs must be the approximation coefficient tensor.")
     levels = []
@@ -35,4 +37,4 @@ def waverec2(coeffs: WaveletCoeff2d, wavelet: Union[Wavelet, str], *, axes: _fwt
                 "tensors as returned by wavedec2."
             )
         levels.append([c[1], c[0], c[2]])  # bands 1,2,3 = 'ad' (V), 'da' (H), 'dd' (D)
-    return _fwt.synthesis(coeffs[0], levels, wavelet, axes, 2, separable=False)
+    return _fwt.synthesis(coeffs[0], levels, wavelet, axes, 2, separable=False, mode=mode)

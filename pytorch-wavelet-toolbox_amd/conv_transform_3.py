@@ -6,12 +6,12 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _fwt
-from .constants import BoundaryMode, Wavelet, WaveletCoeffNd
+from .constants import ExtendedBoundaryMode, Wavelet, WaveletCoeffNd
 
 __all__ = ["wavedec3", "waverec3"]
 
 
-def wavedec3(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: BoundaryMode = "zero",
+def wavedec3(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: ExtendedBoundaryMode = "zero",
              level: Optional[int] = None, axes: Tuple[int, int, int] = (-3, -2, -1)) -> WaveletCoeffNd:
     """Multi-level 3-D analysis; returns ``(cA_n, {"aad",...,"ddd"}_n, ..., {...}_1)``.
 
@@ -22,9 +22,11 @@ def wavedec3(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: Boundary
     return _fwt.pack_dict(layout, approx, bufs, _fwt._KEYS_ND[3])
 
 
-def waverec3(coeffs: WaveletCoeffNd, wavelet: Union[Wavelet, str], *, axes: _fwt.AxisHint = None) -> torch.Tensor:
-    """Inverse of :func:`wavedec3` (src/ptwt/conv_transform_3.py:148-251)."""
+def waverec3(coeffs: WaveletCoeffNd, wavelet: Union[Wavelet, str], *, axes: _fwt.AxisHint = None,
+             mode: Optional[ExtendedBoundaryMode] = None) -> torch.Tensor:
+    """Inverse of :func:`wavedec3` (src/ptwt/conv_transform_3.py:148-251).  ``mode``: ``"periodization"`` inverts a periodized
+    decomposition; None or a padded mode is the padded synthesis, which does not depend on the mode."""
     if len(coeffs) == 0 or not isinstance(coeffs[0], torch.Tensor):
         raise ValueError("First element of coeffs must be the approximation coefficient tensor.")
     levels = _fwt.unpack_dict_levels(coeffs, 3, "wavedec3")
-    return _fwt.synthesis(coeffs[0], levels, wavelet, axes, 3, separable=False)
+    return _fwt.synthesis(coeffs[0], levels, wavelet, axes, 3, separable=False, mode=mode)

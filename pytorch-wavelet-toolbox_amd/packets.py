@@ -23,6 +23,12 @@ lets it (a table filled by measurement; today it keeps every cell on per-level l
 crops an inner node that comes out one sample long, not the root: an input of 67 samples comes back with 68, as in the reference.
 Both ``orthogonalization`` values give the boundary filters in their Gram-Schmidt sign (``matmul_transform.py``); the filter bank is
 read once, on the host, when the object is built; float32 / float64 tensors on a ROCm device.
+
+``mode="periodization"`` (PyWavelets' natural packet mode: nodes do not grow with depth) expands a node by one periodized level
+(``_per.fwd`` / ``_per.inv``, kernel ids 38 / 39; include/mifwt.h): children of ceil(n / 2) samples for ANY n, so the level buffers are
+again those above, a tree level is one launch over all its nodes and ``reconstruct`` one synthesis launch per level, for both values
+of ``separable`` (the same transform under two key maps).  There is no subtree kernel.  ``reconstruct`` crops an inner node that comes
+out one sample long, not the root.  Differentiable w.r.t. the data; a learnable or device-resident filter bank is refused.
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _bwt, _engine, _fwt
+from . import _bwt, _engine, _fwt, _per
 from ._wavelets import as_wavelet, dwt_max_level, filter_length, host_taps
 from .matmul_transform import _bank_taps
 from .matmul_transform_2 import _NON_SEPARABLE
@@ -85,6 +91,7 @@ class _PacketTree(collections.UserDict):
             if self._ndim == 2 and not self.separable:
                 raise NotImplementedError(_NON_SEPARABLE)
             self._banks = tuple(_bwt.bank(taps, self.orthogonalization, which) for which in ("analysis", "synthesis"))
+        self._periodized = isinstance(mode, str) and mode == _fwt.PERIODIZATION
         self._axes = _fwt._ensure_axes(axes, self._ndim)
         self._filter_keys = set(self._bands)
         self.maxlevel: Optional[int] = None
@@ -102,6 +109,8 @@ class _PacketTree(collections.UserDict):
                 raise NotImplementedError(_BOUNDARY_DEVICE)
             if data.dtype not in (torch.float32, torch.float64):
                 raise ValueError(f"Input dtype {data.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
+        if self._periodized:
+            _fwt._per_taps(self.wavelet, data)  # (the refusals that need no device: dtype, learnable / device-resident taps)
         self.data = {}
         self._assigned = set()
         self._layout = _fwt._Layout(data, self._ndim, self._axes)
@@ -195,6 +204,15 @@ class _PacketTree(collections.UserDict):
                 self._store_level(level + 1, out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:]))
             level += k
 
+    def _expand_periodized(self, level: int) -> None:
+        """Every node of ``level + 1`` from ``level`` with ONE periodized analysis launch."""
+        src = self._level_buffer(level)
+        nb = len(self._bands)
+        flat = src.reshape(-1, *src.shape[1 + level:])
+        dec_lo, dec_hi, _, _ = _fwt._per_taps(self.wavelet, flat)
+        out = _per.fwd(flat, dec_lo, dec_hi)  # [B * nb^level, nb, M..]
+        self._store_level(level + 1, out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:]))
+
     # ---- dict protocol ----------------------------------------------------------------------------------------
     def __setitem__(self, key: str, value: torch.Tensor) -> None:
         self._assigned.add(key)
@@ -227,6 +245,9 @@ class _PacketTree(collections.UserDict):
                 start -= 1
             if self._banks is not None:
                 self._expand_boundary(start, len(key))
+            elif self._periodized:
+                for level in range(start, len(key)):
+                    self._expand_periodized(level)
             else:
                 for level in range(start, len(key)):
                     self._expand_level(level)
@@ -241,6 +262,8 @@ class _PacketTree(collections.UserDict):
             self.maxlevel = dwt_max_level(min(self._layout.fold(root).shape[1:]), filter_length(self.wavelet))
         if self._banks is not None:
             return self._reconstruct_boundary()
+        if self._periodized:
+            return self._reconstruct_periodized()
         _, _, rec_lo, rec_hi = host_taps(self.wavelet)
         tap_t = _fwt._tap_tensors(self.wavelet)
         flen = len(rec_lo)
@@ -324,6 +347,25 @@ class _PacketTree(collections.UserDict):
                 rec = _boundary_transposed([flat[:, s] for s in range(nb)], bank, tuple(out_ext))
                 self._replace_level(level - 1, rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:]))
             level -= k
+        return self
+
+    def _reconstruct_periodized(self):
+        """``reconstruct`` with one periodized synthesis launch per level; a node that comes out one sample long is cropped to the
+        extents it had, the root is not."""
+        nb, nd = len(self._bands), self._ndim
+        for level in range(self.maxlevel, 0, -1):
+            self._require_children(level - 1)
+            children = self._level_buffer(level)  # [B, nb^level.., M..]
+            flat = children.reshape(-1, nb, *children.shape[1 + level:])
+            _, _, rec_lo, rec_hi = _fwt._per_taps(self.wavelet, flat)
+            out_ext = [2 * int(c) for c in flat.shape[2:]]
+            target = self._extents_of_level(level - 1) if level > 1 else None
+            if target is None and level > 1:
+                target = self._layout.fold(self[self._keys_of_level(level - 1)[0]]).shape[1:]
+            if target is not None:
+                out_ext = [n - _fwt._adjust_trim(n, int(target[a])) for a, n in enumerate(out_ext)]
+            rec = _per.inv([flat[:, s] for s in range(nb)], rec_lo, rec_hi, out_ext)
+            self._replace_level(level - 1, rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:]))
         return self
 
     def _replace_level(self, level: int, buf: torch.Tensor) -> None:
