@@ -500,6 +500,48 @@ int mifwt_per_axis_inv(int dtype, int filt_len, int64_t outer, int64_t n_out, in
                        const void* hi_in, const int64_t* hi_strides, void* y, const int64_t* y_strides, const double* lo, const double* hi,
                        void* stream);
 
+/* VALUE-MAP extension levels — PyWavelets' modes "smooth", "antisymmetric" and "antireflect" (the reference has none of them): the padded
+ * level of mode "zero" with the zeros replaced by an extension xe whose samples are weighted sums of source samples, so no index map
+ * serves them and `mifwt_mode` does not list them; the entry points take `ext_mode` (MIFWT_EXT_*) next to the descriptor, whose `mode` is
+ * ignored.  Per axis of N samples, xe[i] = x[i] for 0 <= i < N and, with floor division,
+ *     antisymmetric   q, r = divmod(i, N):    q even: x[r];  q odd: -x[N-1-r]                                       (any N >= 1)
+ *     antireflect     q, r = divmod(i, N-1):  q even: x[r] + q (x[N-1] - x[0]);  q odd: -x[N-1-r] + (q+1) x[N-1] - (q-1) x[0];  N = 1: x[0]
+ *     smooth          i < 0: x[0] + i (x[1] - x[0]);  i >= N: x[N-1] + (i-N+1) (x[N-1] - x[N-2]);  N = 1: x[0]
+ * any number of wraps, no pad check.  L even, taps in PyWavelets order:
+ *     analysis    M = floor((N + L - 1) / 2);  cA[k] = sum_j dec_lo[j] xe[2 k + 1 - j],  cD likewise with dec_hi,  0 <= k < M
+ *                 (pads of L - 2 on the left and L - 2 + (N mod 2) on the right, as every padded mode)
+ *     adjoint     T[i] = sum_k dec_lo[2 k + 1 - i] gA[k] + dec_hi[2 k + 1 - i] gD[k] over -(L-2) <= i < N + L - 2 + (N mod 2);
+ *                 g_x[s] = sum_i E[i, s] T[i],  E[i, s] the weight of x[s] in xe[i]
+ * N-D: the 1-D level per transformed axis, separably; band order as everywhere (bit (ndim-1-a) set <=> high-pass along axis a).  Synthesis is
+ * the padded synthesis (mifwt_dwt_inv), which has no mode.
+ *   desc      as for mifwt_per_fwd: sig_extent = N, coef_extent = floor((N + L - 1) / 2) per axis (anything else: MIFWT_ERR_BADARG)
+ *   lo / hi   HOST taps dec_lo / dec_hi, PyWavelets order, for the analysis AND its adjoint
+ * Fused kernels (ids 42 / 43, csrc/mifwt_ext.hip): f32 / f64, even L from 2 to 20, ndim 1 or 2, unit innermost strides, any extent >= 1: one
+ * launch per level, no padded-extent tensor in global memory.  mifwt_ext_supported / mifwt_ext_kernel_id are decided on the host: 1 / the
+ * kernel id where the fused kernels serve the level (direction 0 analysis, 1 adjoint), 0 / MIFWT_ERR_UNSUPPORTED where they do not
+ * (mifwt_ext_fwd / _adj then launch nothing and return MIFWT_ERR_UNSUPPORTED), MIFWT_ERR_BADARG for inconsistent arguments.
+ * mifwt_ext_axis_fwd / _adj: ONE axis of a level through a run-time tap loop (ids 44 / 45): arrays [outer, n, inner] with (outer, axis,
+ * inner) strides in elements, even L <= MIFWT_MAX_FILT, f32 / f64, any n >= 1; the coefficient arrays have floor((n + L - 1) / 2) entries. */
+#define MIFWT_EXT_SMOOTH 0
+#define MIFWT_EXT_ANTISYMMETRIC 1
+#define MIFWT_EXT_ANTIREFLECT 2
+#define MIFWT_KID_EXT_FWD 42       /* fused analysis level, ndim 1 or 2 */
+#define MIFWT_KID_EXT_ADJ 43       /* its adjoint */
+#define MIFWT_KID_EXT_AXIS_FWD 44  /* one axis, any strides, run-time tap loop */
+#define MIFWT_KID_EXT_AXIS_ADJ 45
+int mifwt_ext_supported(const mifwt_level_desc* desc, int ext_mode, int direction);
+int mifwt_ext_kernel_id(const mifwt_level_desc* desc, int ext_mode, int direction);
+int mifwt_ext_fwd(const mifwt_level_desc* desc, int ext_mode, const void* x, void* approx, void* const* details, const double* lo,
+                  const double* hi, void* stream);
+int mifwt_ext_adj(const mifwt_level_desc* desc, int ext_mode, const void* g_approx, const void* const* g_details, void* g_x, const double* lo,
+                  const double* hi, void* stream);
+int mifwt_ext_axis_fwd(int ext_mode, int dtype, int filt_len, int64_t outer, int64_t n, int64_t inner, const void* x, const int64_t* x_strides,
+                       void* lo_out, const int64_t* lo_strides, void* hi_out, const int64_t* hi_strides, const double* lo, const double* hi,
+                       void* stream);
+int mifwt_ext_axis_adj(int ext_mode, int dtype, int filt_len, int64_t outer, int64_t n, int64_t inner, const void* g_lo, const int64_t* lo_strides,
+                       const void* g_hi, const int64_t* hi_strides, void* g_x, const int64_t* x_strides, const double* lo, const double* hi,
+                       void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -559,7 +601,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   32 / 33  a subtree (two or more levels) of a 1-D boundary-wavelet packet tree per launch, analysis / synthesis, one row per workgroup
  *          (mifwt_bwt_tree_fwd / mifwt_bwt_tree_inv; f32 / f64, even L <= 20; answered by mifwt_bwt_tree_levels)
  *   38 / 39  fused periodized analysis / synthesis level, 1-D and 2-D (mifwt_per_fwd / mifwt_per_inv; answered by mifwt_per_kernel_id)
- *   40 / 41  one axis of a periodized level through a run-time tap loop (mifwt_per_axis_fwd / mifwt_per_axis_inv) */
+ *   40 / 41  one axis of a periodized level through a run-time tap loop (mifwt_per_axis_fwd / mifwt_per_axis_inv)
+ *   42 / 43  fused value-map extension analysis level / its adjoint, 1-D and 2-D (mifwt_ext_fwd / mifwt_ext_adj; answered by mifwt_ext_kernel_id)
+ *   44 / 45  one axis of such a level / of its adjoint through a run-time tap loop (mifwt_ext_axis_fwd / mifwt_ext_axis_adj) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).
@@ -593,7 +637,8 @@ int mifwt_pyr_profile_buffer(void* device_buffer);
 
 /* Diagnostic: how many launches of a kernel VARIANT this process has enqueued — variants that share a kernel id (what the tests use to
  * pin "this code path ran"; `variant` out of range: 0).  Values below 16 are variants; the 2-D and 3-D stationary kernels and the
- * periodized kernels (MIFWT_KID_PER_*, 38 .. 41), which have no variants, are counted under their kernel ids. */
+ * periodized and value-map extension kernels (MIFWT_KID_PER_*, MIFWT_KID_EXT_*, 38 .. 45), which have no variants, are counted under
+ * their kernel ids. */
 #define MIFWT_VARIANT_FWD_MFMA_WALK 0 /* id 11: the analysis kernel that walks down column panels */
 #define MIFWT_VARIANT_FWD_MFMA_TILE 1 /* id 11: the tile-at-a-time analysis kernel of round 2 (MIFWT_OPT_MFMA_MODE 3) */
 #define MIFWT_VARIANT_FWD_PYR_ST16 2  /* id 16: 16-byte stores after a lane-pair exchange (planes with 16-byte aligned rows) */

@@ -145,6 +145,16 @@ PER_ENTRIES: dict = {
     "mifwt_per_axis_inv": (_c, [_c, _c, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _vp]),
 }
 
+# The value-map extension levels (_ext.py; include/mifwt.h, mifwt_ext_*): bound privately for the same reason.
+EXT_ENTRIES: dict = {
+    "mifwt_ext_supported": (_c, [_desc_p, _c, _c]),
+    "mifwt_ext_kernel_id": (_c, [_desc_p, _c, _c]),
+    "mifwt_ext_fwd": (_c, [_desc_p, _c, _vp, _vp, _vpp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_ext_adj": (_c, [_desc_p, _c, _vp, _vpp, _vp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_ext_axis_fwd": (_c, [_c, _c, _c, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _vp]),
+    "mifwt_ext_axis_adj": (_c, [_c, _c, _c, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _vp]),
+}
+
 _MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
                    "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
 _abi_mismatch = False

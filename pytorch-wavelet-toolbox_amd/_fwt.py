@@ -822,6 +822,8 @@ def analysis(data: torch.Tensor, wavelet, mode, level: Optional[int], axes: Axis
     """Multi-level analysis.  Returns ``(layout, approx [B,*M], [buffer [B,2^n,*M] per level, coarsest first])``."""
     if isinstance(mode, str) and mode == PERIODIZATION:
         return _analysis_per(data, wavelet, level, axes, ndim)
+    if isinstance(mode, str) and mode in EXT_MODES:
+        return _analysis_ext(data, wavelet, mode, level, axes, ndim)
     axes = _ensure_axes(axes, ndim)
     layout = _Layout(data, ndim, axes)
     x = layout.fold(data)
@@ -1008,7 +1010,7 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
     selects the periodized synthesis; the padded synthesis does not depend on its mode, which is only checked."""
     if isinstance(mode, str) and mode == PERIODIZATION:
         return _synthesis_per(approx, levels, wavelet, axes, ndim, separable)
-    if mode is not None:
+    if mode is not None and not (isinstance(mode, str) and mode in EXT_MODES):
         _mode_id(mode)
     axes = _ensure_axes(axes, ndim)
     layout = _Layout(approx, ndim, axes)
@@ -1141,19 +1143,20 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
 PERIODIZATION = "periodization"
 
 
-def _per_taps(wavelet, proto: torch.Tensor):
-    """The refusals of the periodized mode that need no device, and the bank as host floats (tensor taps are read once)."""
+def _per_taps(wavelet, proto: torch.Tensor, mode: str = PERIODIZATION):
+    """The refusals of the periodized mode (and of the value-map extension modes, ``mode``) that need no device, and the bank as host
+    floats (tensor taps are read once)."""
     if proto.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"Input dtype {proto.dtype} not supported")
     if _tap_tensors(wavelet) is not None:
-        raise NotImplementedError("mode='periodization' does not take a learnable filter bank (taps that require grad)")
+        raise NotImplementedError(f"mode='{mode}' does not take a learnable filter bank (taps that require grad)")
     bank = wavelet if isinstance(wavelet, tuple) else getattr(wavelet, "filter_bank", ())
     tensor_bank = not isinstance(wavelet, str) and len(bank) == 4 and all(isinstance(t, torch.Tensor) for t in bank)
     if tensor_bank and (_wavelets._device_taps_mode == "always" or (proto.is_cuda and device_bank(wavelet, proto.device) is not None)):
-        raise NotImplementedError("mode='periodization' does not take device-resident taps (set_device_taps): its kernels read host taps")
+        raise NotImplementedError(f"mode='{mode}' does not take device-resident taps (set_device_taps): its kernels read host taps")
     taps = host_taps(wavelet)
     if len(taps[0]) != len(taps[2]) or len(taps[0]) % 2:
-        raise ValueError("mode='periodization' needs dec and rec filters of one even length")
+        raise ValueError(f"mode='{mode}' needs dec and rec filters of one even length")
     return taps
 
 
@@ -1207,6 +1210,33 @@ def _synthesis_per(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavel
             out_ext = [n - _adjust_trim(n, int(nxt[1 + a])) for a, n in enumerate(out_ext)]
         cur = _per.inv([cur, *det], rec_lo, rec_hi, out_ext)
     return layout.unfold(cur)
+
+
+# ------------------------------------------------------------------------------------------ smooth / antisymmetric / antireflect
+# PyWavelets' three value-map extension modes (include/mifwt.h, _ext.py): padded levels — floor((n + L - 1) / 2) coefficients per axis, the
+# padded synthesis inverts them — whose extension no index map expresses.  Not among _engine.MODE_IDS either: one level call per trip.
+EXT_MODES = ("smooth", "antisymmetric", "antireflect")
+
+
+def _analysis_ext(data: torch.Tensor, wavelet, mode: str, level: Optional[int], axes: AxisHint, ndim: int):
+    from . import _ext
+
+    axes = _ensure_axes(axes, ndim)
+    layout = _Layout(data, ndim, axes)
+    dec_lo, dec_hi, _, _ = _per_taps(wavelet, data, mode)
+    x = layout.fold(data)
+    if level is None:
+        level = dwtn_max_level(x.shape[1:], len(dec_lo))
+    elif level < 0:
+        raise ValueError(f"Level value of {level} is too low. Minimum level is 0.")
+    _engine._require_gpu(x)
+    bufs: list = []  # coarsest level first
+    cur = x
+    for _ in range(level):
+        buf = _ext.fwd(cur, dec_lo, dec_hi, mode)
+        bufs.insert(0, buf)
+        cur = buf[:, 0]
+    return layout, cur, bufs
 
 
 # ------------------------------------------------------------------------------------------ containers

@@ -63,8 +63,11 @@ def supported_dtypes():
 #: mirror) | periodic | symmetric (half-sample mirror)
 BoundaryMode = Literal["constant", "zero", "reflect", "periodic", "symmetric"]
 #: the padded modes and PyWavelets' ``"periodization"``: ``ceil(N / 2)`` coefficients per axis and level, exactly orthogonal for
-#: orthogonal wavelets (an engine extension; the ``Matrix*`` classes keep taking :data:`BoundaryMode` only)
-ExtendedBoundaryMode = Union[BoundaryMode, Literal["periodization"]]
+#: orthogonal wavelets (``_per.py``), and PyWavelets' ``"smooth"`` (a straight line through the two edge samples), ``"antisymmetric"``
+#: (the half-sample mirror, negated) and ``"antireflect"`` (the point reflection about the edge samples), which are padded modes whose
+#: extension adds weighted samples (``_ext.py``; the padded synthesis inverts them).  Engine extensions: the ``Matrix*`` classes keep
+#: taking :data:`BoundaryMode` only
+ExtendedBoundaryMode = Union[BoundaryMode, Literal["periodization", "smooth", "antisymmetric", "antireflect"]]
 
 
 class Wavelet(Protocol):

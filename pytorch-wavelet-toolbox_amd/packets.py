@@ -29,6 +29,9 @@ read once, on the host, when the object is built; float32 / float64 tensors on a
 again those above, a tree level is one launch over all its nodes and ``reconstruct`` one synthesis launch per level, for both values
 of ``separable`` (the same transform under two key maps).  There is no subtree kernel.  ``reconstruct`` crops an inner node that comes
 out one sample long, not the root.  Differentiable w.r.t. the data; a learnable or device-resident filter bank is refused.
+
+``mode="smooth"`` / ``"antisymmetric"`` / ``"antireflect"`` are padded modes: the level buffers, keys and ``reconstruct`` of the padded
+modes, with ``_ext.fwd`` (kernel ids 42 / 44) as the level call; the same refusals as ``"periodization"``.
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _bwt, _engine, _fwt, _per
+from . import _bwt, _engine, _ext, _fwt, _per
 from ._wavelets import as_wavelet, dwt_max_level, filter_length, host_taps
 from .matmul_transform import _bank_taps
 from .matmul_transform_2 import _NON_SEPARABLE
@@ -92,6 +95,7 @@ class _PacketTree(collections.UserDict):
                 raise NotImplementedError(_NON_SEPARABLE)
             self._banks = tuple(_bwt.bank(taps, self.orthogonalization, which) for which in ("analysis", "synthesis"))
         self._periodized = isinstance(mode, str) and mode == _fwt.PERIODIZATION
+        self._extended = isinstance(mode, str) and mode in _fwt.EXT_MODES
         self._axes = _fwt._ensure_axes(axes, self._ndim)
         self._filter_keys = set(self._bands)
         self.maxlevel: Optional[int] = None
@@ -111,6 +115,8 @@ class _PacketTree(collections.UserDict):
                 raise ValueError(f"Input dtype {data.dtype} not supported by the boundary-wavelet transforms (float32 / float64)")
         if self._periodized:
             _fwt._per_taps(self.wavelet, data)  # (the refusals that need no device: dtype, learnable / device-resident taps)
+        if self._extended:
+            _fwt._per_taps(self.wavelet, data, self.mode)
         self.data = {}
         self._assigned = set()
         self._layout = _fwt._Layout(data, self._ndim, self._axes)
@@ -161,6 +167,11 @@ class _PacketTree(collections.UserDict):
         src = self._level_buffer(level)
         nb = len(self._bands)
         flat = src.reshape(-1, *src.shape[1 + level:])
+        if self._extended:  # (smooth / antisymmetric / antireflect: the same level call as wavedec*, _ext.py)
+            dec_lo, dec_hi, _, _ = _fwt._per_taps(self.wavelet, flat, self.mode)
+            out = _ext.fwd(flat, dec_lo, dec_hi, self.mode)
+            self._store_level(level + 1, out.reshape(src.shape[0], *([nb] * (level + 1)), *out.shape[2:]))
+            return
         dec_lo, dec_hi, _, _ = host_taps(self.wavelet)
         mode_id = _fwt._mode_id(self.mode)
         _fwt._check_pad(flat.shape[1:], len(dec_lo), "reflect" if self.mode is None else self.mode)
