@@ -48,7 +48,19 @@ extern "C" {
 #define MIFWT_MAX_NDIM 3
 #define MIFWT_MAX_FILT 128 /* longest PyWavelets discrete filter is coif17 = 102 taps */
 
-enum mifwt_dtype { MIFWT_F32 = 0, MIFWT_F64 = 1, MIFWT_F16 = 2 /* f16 storage, f32 arithmetic */ };
+enum mifwt_dtype {
+  MIFWT_F32 = 0,
+  MIFWT_F64 = 1,
+  MIFWT_F16 = 2, /* f16 storage, f32 arithmetic */
+  MIFWT_BF16 = 3 /* bf16 storage, f32 arithmetic */
+};
+/* The two 16-bit STORAGE types go together: every entry point that takes MIFWT_F16 takes MIFWT_BF16, runs it on the same kernel id (a
+ * bf16 instantiation of that kernel) and rounds where the f16 form rounds — mifwt_dwt_fwd / _inv and their adjoints (kernel ids 0, 3 - 8,
+ * 11, 23), mifwt_kernel_id, mifwt_workspace_bytes, mifwt_swt_fwd / mifwt_swt_inv.  Every entry point that answers MIFWT_ERR_UNSUPPORTED
+ * (or 0 from a *_supported query) for MIFWT_F16 answers the same for MIFWT_BF16, never MIFWT_ERR_BADARG: the multi-level launches,
+ * mifwt_dwt1_*_outer, mifwt_swt2_* / mifwt_swt3_*, mifwt_tap_correlate*, mifwt_per_*, mifwt_ext_*, mifwt_bwt_*, mifwt_bwt3_* and
+ * mifwt_bwt_tree_*.  The device-tap entry points (_dtaps) take both types where their kernels do (ids 0, 3, 4, 7, 8).  Added within ABI
+ * version 3: a new enumerator changes no existing call. */
 
 /* Boundary rules of ptwt.constants.BoundaryMode (src/ptwt/constants.py:85-108, _util.py:36-44). */
 enum mifwt_mode {
@@ -308,7 +320,7 @@ int mifwt_dwt_inv_adjoint(const mifwt_level_desc* desc, const void* g_y, void* g
  * elements, dilation = 2^level_index, periodic extension as an index map.  `scale` multiplies the result: 1 for swt,
  * 0.5 for iswt (the reference's mean over the two reconstructions); with reversed taps and the other scale each
  * call is the adjoint of the other (backward passes).  Even filt_len <= MIFWT_MAX_FILT (2..20 unrolled, longer
- * filters through a run-time tap loop), f32 / f64 / f16.
+ * filters through a run-time tap loop), f32 / f64 / f16 / bf16.
  *   fwd: lo/hi[n] = scale * sum_m dec_lo/hi[m] x[(n + D (L/2 - m)) mod N]
  *   inv: y[n]     = scale * sum_j rec_lo[j] a[(n + D (L/2 - 1 - j)) mod N] + rec_hi[j] d[(same)] */
 int mifwt_swt_fwd(int dtype, int filt_len, int64_t rows, int64_t n, int64_t dilation, const void* x, int64_t x_row_stride,
@@ -567,12 +579,12 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
 
 /* Which kernel family a call would dispatch to (tests use it to assert the fast path is the one that ran);
  * negative = error code.
- *   0  generic per-axis passes (any strides, any L <= 128; f32 / f64 / f16 storage — the fallback of every call no fused kernel takes)
+ *   0  generic per-axis passes (any strides, any L <= 128; f32 / f64 / f16 / bf16 storage — the fallback of every call no fused kernel takes)
  *   1 / 2  fused single-launch 2-D analysis / synthesis level, streaming wave strips (f32, even L <= 16)
- *   7 / 8  fused single-launch 2-D analysis / synthesis level, LDS tiles (f32 / f16, even L <= 20, 24, 32; f64, even L <= 16); the
+ *   7 / 8  fused single-launch 2-D analysis / synthesis level, LDS tiles (f32 / f16 / bf16, even L <= 20, 24, 32; f64, even L <= 16); the
  *          default 2-D kernels — the streaming analysis kernel is kept for 16-tap filters on planes >= ~1500^2
  *   3 / 4  streaming axis passes, analysis / synthesis: inner-axis kernel (+ one outer-axis pass per further
- *          axis); unit innermost stride, f32 / f64 / f16, L in {2..20 even, 24, 32}
+ *          axis); unit innermost stride, f32 / f64 / f16 / bf16, L in {2..20 even, 24, 32}
  *   5 / 6  3-D analysis / synthesis (f32, even L <= 16; what the brick kernels 9 / 10 do not take): fused 2-D kernel over every
  *          depth slice + one streaming pass along depth
  *   9 / 10  fully fused 3-D analysis / synthesis level, LDS bricks (f32, L in {2, 4, 6}; synthesis also 8): the small volumes
@@ -582,7 +594,7 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          on for <= 4 / 6 / 8 taps, synthesis from 2^16 (<= 4 taps) / 2^19 output samples on).  Round 6: batches of 8 / 16 volumes and
  *          more from 2^21 / 10^5 samples per volume on (L <= 6); a SLAB form of the analysis kernel for 8 / 10 taps on rows of at most
  *          128 samples (f32, every mode: a workgroup filters every staged row once), picked by volume and batch (mifwt_dwt3_fwd_slab_plan)
- *   11 / 23  fused 2-D analysis / synthesis level on the matrix cores (banded-Toeplitz MFMA; f16 storage, even L in [18, 32]; both walk down
+ *   11 / 23  fused 2-D analysis / synthesis level on the matrix cores (banded-Toeplitz MFMA; f16 / bf16 storage, even L in [18, 32]; both walk down
  *          column panels; the synthesis kernel from 16 tiles of 32 x 128 samples per call on, the vector tile kernel 8 below that)
  *   12 / 13  two fused 2-D analysis / synthesis levels per launch (mifwt_dwt2_fwd_pair / mifwt_dwt2_inv_pair; never
  *          returned by mifwt_kernel_id, which describes single-level calls)
@@ -617,7 +629,7 @@ int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 #define MIFWT_OPT_NT_STORE 4       /* non-zero: nontemporal stores for the sub-band planes */
 #define MIFWT_OPT_TILE_MODE 5      /* 2-D analysis: 0 = auto (LDS-tile kernel on small planes), 1 = always tile, 2 = never.  3-D: 0 = auto (depth-walking kernels 24 / 25 on big volumes, bricks 9 / 10 on small ones), 1 = bricks wherever they can run, 2 = composed route, 4 = walking kernels wherever they can run */
 #define MIFWT_OPT_TILE_ROWS 6      /* >0 overrides the tile kernels' output rows per tile */
-#define MIFWT_OPT_MFMA_MODE 7      /* 2-D analysis, f16 storage, 18..32 taps: 0 = matrix-core kernels (walking down column panels), 2 = vector tile
+#define MIFWT_OPT_MFMA_MODE 7      /* 2-D analysis, f16 / bf16 storage, 18..32 taps: 0 = matrix-core kernels (walking down column panels), 2 = vector tile
                                       kernels, 3 = the tile-at-a-time analysis kernel of round 2 (comparisons), 4 = the synthesis kernel for every size */
 #define MIFWT_OPT_PAIR_MODE 8      /* multi-level launches (mifwt_dwt2_fwd_pyramid, mifwt_dwt2_fwd_pair, mifwt_dwt2_inv_pair, mifwt_dwt1_fwd_tail): 2 = never (they answer
                                       UNSUPPORTED / 0); analysis pairs: 0 = auto (rolling strips for 8 taps, else tiles), 1 = tiles only,

@@ -21,7 +21,7 @@ if "MIFWT_LIB" in os.environ:
 ABI_VERSION = 3
 
 MODE_IDS = {"zero": 0, "constant": 1, "reflect": 2, "periodic": 3, "symmetric": 4}
-_DTYPE_IDS = {torch.float32: 0, torch.float64: 1, torch.float16: 2}
+_DTYPE_IDS = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}
 
 _i64x3 = ctypes.c_int64 * 3
 _i64x4 = ctypes.c_int64 * 4
@@ -489,12 +489,12 @@ class HipLevelEngine:
         # rows of the sub-band planes can be made to start on ROW_ALIGN-byte boundaries (pitch padded, the
         # returned bands are views of the padded buffer).  Measured on MI355X: no gain at 16 B, a loss at 128 B
         # (config 2), so the default is dense rows.
-        # Exception: the matrix-core analysis kernel (f16 storage, 18..32 taps, 2-D) stores 16 bytes per lane; with the dense pitch of
+        # Exception: the matrix-core analysis kernel (f16 / bf16 storage, 18..32 taps, 2-D) stores 16 bytes per lane; with the dense pitch of
         # an odd coefficient width every other row starts 2-byte aligned and the stores are split: level 1 of the config-5 slice
         # 4.3 ms dense, 3.7 ms with 16-byte, 2.76 ms with 128-byte aligned rows (tools/mfma_walk_parts.py) — those planes get 128.
         esz = x.element_size()
         align = max(ROW_ALIGN, min_align, 1)
-        if align <= 1 and ndim == 2 and x.dtype == torch.float16 and 18 <= flen <= 32:
+        if align <= 1 and ndim == 2 and x.dtype in (torch.float16, torch.bfloat16) and 18 <= flen <= 32:
             align = 128
         pitch = -(-coef[-1] * esz // align) * align // esz if align > esz and ndim >= 2 else coef[-1]
         if min_align < 0 and ndim >= 2:  # (experiments, tools/pitch_sweep.py: -k = k extra elements per row, whatever the alignment)

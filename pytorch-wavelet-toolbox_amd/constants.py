@@ -27,9 +27,13 @@ __all__ = [
 
 #: dtypes the reference accepts (src/ptwt/constants.py:27); anything else raises ``ValueError``.
 SUPPORTED_DTYPES = {torch.float32, torch.float64}
+#: the 16-bit storage types of :func:`half_storage`
+HALF_STORAGE_DTYPES = {torch.float16, torch.bfloat16}
 
-#: Engine extension (NOT in the reference, which raises ``ValueError`` for it): float16 STORAGE with float32
-#: arithmetic (C ABI ``MIFWT_F16``).  Off by default so that error behaviour matches the reference.  Switched on for a
+#: Engine extension (NOT in the reference, which raises ``ValueError`` for it): 16-bit STORAGE with float32 arithmetic,
+#: ``torch.float16`` (C ABI ``MIFWT_F16``) and ``torch.bfloat16`` (``MIFWT_BF16``).  "half" in the names below means "16-bit
+#: storage", either type: bfloat16 follows float16 route by route (same kernel ids, same refusals), with float32's range
+#: and a unit roundoff of 2^-8 instead of 2^-11.  Off by default so that error behaviour matches the reference.  Switched on for a
 #: scope with :func:`half_storage` (a context manager over a ``contextvars`` variable: local to the thread / task, so
 #: one caller's fp16 workload does not change what another thread's call accepts); :func:`set_half_storage` sets the
 #: process-wide DEFAULT the scoped value falls back to (BASELINE.json configs[4] is an fp16 workload).
@@ -38,15 +42,17 @@ _half_storage_scoped: "contextvars.ContextVar[object]" = contextvars.ContextVar(
 
 
 def set_half_storage(enabled: bool) -> None:
-    """Process-wide default: accept ``torch.float16`` inputs (coefficients are returned in float16, accumulated in
-    float32).  Prefer ``with ptwt_amd.half_storage(): ...`` — scoped, thread-local."""
+    """Process-wide default: accept the 16-bit storage types, ``torch.float16`` and ``torch.bfloat16`` ("half" = 16-bit storage;
+    coefficients are returned in the input's dtype, accumulated in float32).  Prefer ``with ptwt_amd.half_storage(): ...`` — scoped,
+    thread-local."""
     global _half_storage_default
     _half_storage_default = bool(enabled)
 
 
 @contextlib.contextmanager
 def half_storage(enabled: bool = True):
-    """``with half_storage():`` — calls in this scope (this thread / task only) accept ``torch.float16`` tensors."""
+    """``with half_storage():`` — calls in this scope (this thread / task only) accept 16-bit storage: ``torch.float16`` and
+    ``torch.bfloat16`` tensors ("half" = 16-bit storage, float32 arithmetic)."""
     token = _half_storage_scoped.set(bool(enabled))
     try:
         yield
@@ -57,7 +63,7 @@ def half_storage(enabled: bool = True):
 def supported_dtypes():
     scoped = _half_storage_scoped.get()
     on = _half_storage_default if scoped is None else scoped
-    return SUPPORTED_DTYPES | {torch.float16} if on else SUPPORTED_DTYPES
+    return SUPPORTED_DTYPES | HALF_STORAGE_DTYPES if on else SUPPORTED_DTYPES
 
 #: boundary rules (src/ptwt/constants.py:85): zero | constant (edge replicate) | reflect (whole-sample
 #: mirror) | periodic | symmetric (half-sample mirror)

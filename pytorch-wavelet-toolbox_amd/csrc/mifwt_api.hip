@@ -11,12 +11,12 @@ using namespace mifwt;
 
 namespace {
 
-inline int64_t elem_size(int dtype) { return dtype == MIFWT_F64 ? 8 : (dtype == MIFWT_F16 ? 2 : 4); }
+inline int64_t elem_size(int dtype) { return dtype == MIFWT_F64 ? 8 : (is_storage16(dtype) ? 2 : 4); }
 
 int validate(const mifwt_level_desc* d, int direction) {
   if (!d) return MIFWT_ERR_BADARG;
   if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && d->dtype != MIFWT_F16) return MIFWT_ERR_BADARG;
+  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
   if (d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT) return MIFWT_ERR_BADARG;
   if (d->batch < 0) return MIFWT_ERR_BADARG;
   if (direction == 0 && (d->mode < MIFWT_MODE_ZERO || d->mode > MIFWT_MODE_SYMMETRIC)) return MIFWT_ERR_BADARG;

@@ -11,7 +11,7 @@
 //     it loads itself; neighbouring lanes' windows overlap, the overlap is served by the vector L1.  Boundary
 //     lanes (window leaves [0, N)) take a per-element index-mapped path.  This is the 1-D transform
 //     (wavedec / waverec, reference src/ptwt/conv_transform.py:135-139, :184-199).
-// Templated on the storage type T (float, double, _Float16 with float arithmetic) and the even filter
+// Templated on the storage type T (float, double, _Float16 / __bf16 with float arithmetic) and the even filter
 // length L; (lo, hi) taps travel in the kernel arguments.
 //
 // Math:
@@ -38,6 +38,12 @@ struct ElemTraits<double> {
 };
 template <>
 struct ElemTraits<_Float16> {
+  using Acc = float;
+  static constexpr int EV = 8;
+  static constexpr int EO = 4;
+};
+template <>
+struct ElemTraits<__bf16> {
   using Acc = float;
   static constexpr int EV = 8;
   static constexpr int EO = 4;

@@ -350,7 +350,7 @@ constexpr int kMaxFused3 = 8;  // longest filter of the fused 3-D kernels
 int fused3_check(const mifwt_level_desc* d) {
   if (!d) return MIFWT_ERR_BADARG;
   if (d->ndim != 3 || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0) return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && d->dtype != MIFWT_F16) return MIFWT_ERR_BADARG;
+  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
   if (d->mode < MIFWT_MODE_ZERO || d->mode > MIFWT_MODE_SYMMETRIC) return MIFWT_ERR_BADARG;
   for (int ax = 0; ax < 3; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];

@@ -249,7 +249,7 @@ int tree_dispatch(int filt_len, int inverse, int64_t rows, int n, int64_t in_rs,
 
 int tree_call(int inverse, int dtype, int filt_len, int64_t rows, int64_t n, int64_t in_rs, int nlevels, const void* in,
               void* const* levels, const double* lo, const double* hi, const mifwt_bwt_tables* tb, void* stream) {
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return dtype == MIFWT_F16 ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
+  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return is_storage16(dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
   if (filt_len < 2 || filt_len > MIFWT_MAX_FILT || rows < 0 || n < 1) return MIFWT_ERR_BADARG;
   if (!in || !levels || !lo || !hi || !tb || !tb->rows) return MIFWT_ERR_BADARG;
   if (nlevels < 2 || (filt_len & 1) || filt_len > 20 || tree_levels(dtype, filt_len, n, nlevels) != nlevels) return MIFWT_ERR_UNSUPPORTED;

@@ -10,6 +10,8 @@
 namespace mifwt {
 
 constexpr int kMaxFilt = MIFWT_MAX_FILT;
+// the two 16-bit storage types (f32 arithmetic): MIFWT_BF16 follows MIFWT_F16 route by route
+inline bool is_storage16(int dtype) { return dtype == MIFWT_F16 || dtype == MIFWT_BF16; }
 extern int g_options[16];  // mifwt_set_option() switches
 
 // DIAGNOSTICS.  The measurement switches that break results (no stores / no loads / no deep levels ..., MIFWT_OPT_DEBUG), the experiment
@@ -215,7 +217,7 @@ struct StreamCall {
 
 enum StreamKind { kOuterFwd = 0, kOuterInv = 1, kInnerFwd = 2, kInnerInv = 3 };
 bool stream_filter_supported(int filt_len);
-int stream_call(int dtype, int kind, const StreamCall& c);  // dispatches on dtype (f32 / f64 / f16) and filt_len
+int stream_call(int dtype, int kind, const StreamCall& c);  // dispatches on dtype (f32 / f64 / f16 / bf16) and filt_len
 
 // ---- fused fast paths --------------------------------------------------------------------------------
 // Each returns MIFWT_ERR_UNSUPPORTED when the descriptor is outside its envelope (the dispatcher then
@@ -232,7 +234,7 @@ bool dwt2_fwd_tile_supported(const mifwt_level_desc* d);
 int dwt2_fwd_tile(const mifwt_level_desc* d, const void* x, void* approx, void* const* details, LevelTaps dec, hipStream_t stream,
                   BatchSplit split = {0, 0});
 
-// matrix-core (banded-Toeplitz MFMA) fused 2-D analysis level: f16 storage, even L in [18, 32]
+// matrix-core (banded-Toeplitz MFMA) fused 2-D analysis level: f16 / bf16 storage, even L in [18, 32]
 bool dwt2_fwd_mfma_supported(const mifwt_level_desc* d);
 // ... and its synthesis mirror (mifwt_dwt2_inv_mfma.hip, kernel id 23)
 bool dwt2_inv_mfma_supported(const mifwt_level_desc* d);

@@ -6,7 +6,7 @@
 //                                            (replaces F.conv3d / F.conv_transpose3d of the reference,
 //                                            src/ptwt/conv_transform_3.py:127, :218); scratch = 4 planes per
 //                                            slice, traffic = 2x the algorithmic bytes
-//   kDwt1FwdRow / kDwt1InvRow        (3, 4)  unit innermost stride and L in the streaming set, f32 / f64 / f16:
+//   kDwt1FwdRow / kDwt1InvRow        (3, 4)  unit innermost stride and L in the streaming set, f32 / f64 / f16 / bf16:
 //                                            the inner-axis pass (the whole transform in 1-D: F.conv1d /
 //                                            F.conv_transpose1d, src/ptwt/conv_transform.py:137, :187) plus
 //                                            one outer-axis pass per further axis through dense scratch
@@ -21,6 +21,7 @@ namespace mifwt {
 MIFWT_STREAM_LENGTHS(MIFWT_DECL, f32)
 MIFWT_STREAM_LENGTHS(MIFWT_DECL, f64)
 MIFWT_STREAM_LENGTHS(MIFWT_DECL, f16)
+MIFWT_STREAM_LENGTHS(MIFWT_DECL, bf16)
 #undef MIFWT_DECL
 
 bool stream_filter_supported(int L) {
@@ -39,6 +40,9 @@ int stream_call(int dtype, int kind, const StreamCall& c) {
     case MIFWT_F16:
       switch (c.filt_len) { MIFWT_STREAM_LENGTHS(MIFWT_CASE, f16) default: break; }
       break;
+    case MIFWT_BF16:
+      switch (c.filt_len) { MIFWT_STREAM_LENGTHS(MIFWT_CASE, bf16) default: break; }
+      break;
     default: break;
   }
 #undef MIFWT_CASE
@@ -47,7 +51,7 @@ int stream_call(int dtype, int kind, const StreamCall& c) {
 
 namespace {
 
-inline int64_t elem_size(int dtype) { return dtype == MIFWT_F64 ? 8 : (dtype == MIFWT_F16 ? 2 : 4); }
+inline int64_t elem_size(int dtype) { return dtype == MIFWT_F64 ? 8 : (is_storage16(dtype) ? 2 : 4); }
 
 // axes from..nd-1 form one dense run (innermost stride 1, each outer one = product of the inner extents)
 inline bool dense_under(const int64_t* stride, const int64_t* ext, int nd, int from) {
@@ -89,6 +93,7 @@ mifwt_level_desc plane_desc(const mifwt_level_desc* d, int64_t depth, bool* fold
 // ---- LDS-tile fused 2-D analysis: envelope and per-(type, length) instantiation units ---------------------------
 int dwt2_fwd_tile_f32_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
 int dwt2_fwd_tile_f16_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
+int dwt2_fwd_tile_bf16_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
 int dwt2_fwd_tile_f64_short(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
 int dwt2_fwd_tile_long18(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
 int dwt2_fwd_tile_long20(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
@@ -96,7 +101,7 @@ int dwt2_fwd_tile_long24(const mifwt_level_desc*, const void*, void*, void* cons
 int dwt2_fwd_tile_long32(const mifwt_level_desc*, const void*, void*, void* const*, LevelTaps, BatchSplit, hipStream_t);
 
 bool dwt2_fwd_tile_supported(const mifwt_level_desc* d) {
-  if (d->ndim != 2 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F16 && d->dtype != MIFWT_F64)) return false;
+  if (d->ndim != 2 || (d->dtype != MIFWT_F32 && !is_storage16(d->dtype) && d->dtype != MIFWT_F64)) return false;
   const int L = d->filt_len;
   if (!((L >= 2 && L <= 20 && (L & 1) == 0) || L == 24 || L == 32)) return false;
   if (d->dtype == MIFWT_F64 && L > 16) return false;  // f64 instantiations: mifwt_dwt2_fwd_tile_f64.hip
@@ -125,13 +130,14 @@ int dwt2_fwd_tile(const mifwt_level_desc* d, const void* x, void* approx, void* 
     case 32: return dwt2_fwd_tile_long32(d, x, approx, details, t, split, stream);
     default: break;
   }
+  if (d->dtype == MIFWT_BF16) return dwt2_fwd_tile_bf16_short(d, x, approx, details, t, split, stream);
   return d->dtype == MIFWT_F16 ? dwt2_fwd_tile_f16_short(d, x, approx, details, t, split, stream)
                                : dwt2_fwd_tile_f32_short(d, x, approx, details, t, split, stream);
 }
 
 // Two fused 2-D analysis kernels.  Measured on MI355X (64-image batches, 128^2 .. 4096^2 planes): the LDS-tile kernel
 // wins for every L <= 14 (by 4-35 %) and for L = 16 up to ~1500^2 planes; only 16-tap filters on big planes favour
-// the streaming kernel (its register ring re-reads no row halo).  f16 storage and 18..32 taps: tile kernel only.
+// the streaming kernel (its register ring re-reads no row halo).  f16 / bf16 storage and 18..32 taps: tile kernel only.
 int dwt2_fwd_choice(const mifwt_level_desc* d) {
   const int tm = g_options[MIFWT_OPT_TILE_MODE];  // 0 auto, 1 always tile, 2 never tile
   if (g_options[MIFWT_OPT_MFMA_MODE] != 2 && dwt2_fwd_mfma_supported(d)) return kDwt2FwdMfma;
@@ -168,12 +174,13 @@ int dwt2_fwd_fused(const mifwt_level_desc* d, const void* x, void* approx, void*
 // ---- LDS-tile fused 2-D synthesis -------------------------------------------------------------------------------------
 int idwt2_tile_f32_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
 int idwt2_tile_f16_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
+int idwt2_tile_bf16_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
 int idwt2_tile_f64_short(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
 int idwt2_tile_long_a(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
 int idwt2_tile_long_b(const mifwt_level_desc*, const void*, const void* const*, void*, LevelTaps, hipStream_t);
 
 bool dwt2_inv_tile_supported(const mifwt_level_desc* d) {
-  if (d->ndim != 2 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F16 && d->dtype != MIFWT_F64)) return false;
+  if (d->ndim != 2 || (d->dtype != MIFWT_F32 && !is_storage16(d->dtype) && d->dtype != MIFWT_F64)) return false;
   const int L = d->filt_len;
   if (!((L >= 2 && L <= 20 && (L & 1) == 0) || L == 24 || L == 32)) return false;
   if (d->dtype == MIFWT_F64 && L > 16) return false;  // f64 instantiations: mifwt_idwt2_tile_f64.hip
@@ -191,6 +198,7 @@ int dwt2_inv_tile(const mifwt_level_desc* d, const void* approx, const void* con
   if (d->dtype == MIFWT_F64) return idwt2_tile_f64_short(d, approx, details, y, t, stream);
   if (d->filt_len == 18 || d->filt_len == 20) return idwt2_tile_long_a(d, approx, details, y, t, stream);
   if (d->filt_len == 24 || d->filt_len == 32) return idwt2_tile_long_b(d, approx, details, y, t, stream);
+  if (d->dtype == MIFWT_BF16) return idwt2_tile_bf16_short(d, approx, details, y, t, stream);
   return d->dtype == MIFWT_F16 ? idwt2_tile_f16_short(d, approx, details, y, t, stream)
                                : idwt2_tile_f32_short(d, approx, details, y, t, stream);
 }

@@ -71,6 +71,10 @@ template <>
 __device__ __forceinline__ float tile_load<_Float16>(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
   return (float)__builtin_bit_cast(_Float16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, soff, 0));
 }
+template <>
+__device__ __forceinline__ float tile_load<__bf16>(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
+  return (float)__builtin_bit_cast(__bf16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, soff, 0));
+}
 
 template <typename T, int L, int TR>
 __global__ void __launch_bounds__(256, tile_occupancy(L, TR, sizeof(typename TileArith<T>::type))) dwt2_fwd_tile_kernel(const Dwt2TileArgs<T, L> a) {

@@ -504,7 +504,7 @@ int fused_check(const mifwt_level_desc* d, int ext_mode) {
   if (!d || !mode_ok(ext_mode)) return MIFWT_ERR_BADARG;
   if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0)
     return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && d->dtype != MIFWT_F16) return MIFWT_ERR_BADARG;
+  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
   for (int ax = 0; ax < d->ndim; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];
     if (n < 1 || m != (n + d->filt_len - 1) / 2) return MIFWT_ERR_BADARG;
@@ -622,7 +622,7 @@ int ext_axis(int adjoint, int ext_mode, int dtype, int filt_len, int64_t outer, 
              void* stream) {
   if (!in0 || !out0 || (adjoint ? !in1 : !out1) || !sig_s || !lo_s || !hi_s || !lo || !hi || !mode_ok(ext_mode)) return MIFWT_ERR_BADARG;
   if (filt_len < 2 || (filt_len & 1) || filt_len > MIFWT_MAX_FILT || outer < 0 || inner < 0 || n < 1) return MIFWT_ERR_BADARG;
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return dtype == MIFWT_F16 ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
+  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return is_storage16(dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
   if (n > INT32_MAX / 4) return MIFWT_ERR_UNSUPPORTED;
   AxisArgs a;
   a.in0 = in0;

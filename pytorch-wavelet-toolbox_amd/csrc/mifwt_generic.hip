@@ -1,7 +1,7 @@
 // mifwt_generic.hip — generic per-axis analysis / synthesis kernels for gfx950.
 //
 // The catch-all behind the fused fast paths: one transformed axis per launch, any filter length up to
-// 128 taps, any boundary mode, arbitrary element strides, f32 / f64 in their own precision and f16 STORAGE with f32 arithmetic (the
+// 128 taps, any boundary mode, arbitrary element strides, f32 / f64 in their own precision and f16 / bf16 STORAGE with f32 arithmetic (the
 // intermediate passes of an N-D level are then rounded to f16 like every other f16 path of the library).  A thread owns one output
 // coefficient position and produces the low- and high-pass value together (analysis), or one output
 // sample (synthesis, polyphase gather: only the L/2 non-zero products of the transposed convolution are
@@ -228,6 +228,7 @@ int launch_axis_fwd(int dtype, const AxisJob* jobs, int njobs, const int64_t out
   if (dtype == MIFWT_F32) return launch_axis<float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
   if (dtype == MIFWT_F64) return launch_axis<double>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
   if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
+  if (dtype == MIFWT_BF16) return launch_axis<__bf16, float>(0, jobs, njobs, out_ext, taxis, n_in, mode, filt_len, taps, stream);
   return MIFWT_ERR_UNSUPPORTED;
 }
 
@@ -236,6 +237,7 @@ int launch_axis_inv(int dtype, const AxisJob* jobs, int njobs, const int64_t out
   if (dtype == MIFWT_F32) return launch_axis<float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
   if (dtype == MIFWT_F64) return launch_axis<double>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
   if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
+  if (dtype == MIFWT_BF16) return launch_axis<__bf16, float>(1, jobs, njobs, out_ext, taxis, m_in, 0, filt_len, taps, stream);
   return MIFWT_ERR_UNSUPPORTED;
 }
 
@@ -244,6 +246,7 @@ int launch_axis_adj(int dtype, const AxisJob* jobs, int njobs, const int64_t out
   if (dtype == MIFWT_F32) return launch_axis<float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
   if (dtype == MIFWT_F64) return launch_axis<double>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
   if (dtype == MIFWT_F16) return launch_axis<_Float16, float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
+  if (dtype == MIFWT_BF16) return launch_axis<__bf16, float>(2, jobs, njobs, out_ext, taxis, m_in, mode, filt_len, taps, stream, n_sig);
   return MIFWT_ERR_UNSUPPORTED;
 }
 

@@ -52,6 +52,10 @@ template <>
 __device__ __forceinline__ float idwt_tile_load<_Float16>(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
   return (float)__builtin_bit_cast(_Float16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, soff, 0));
 }
+template <>
+__device__ __forceinline__ float idwt_tile_load<__bf16>(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
+  return (float)__builtin_bit_cast(__bf16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, soff, 0));
+}
 
 template <typename T, int L, int TRO>
 __global__ void __launch_bounds__(256, idwt_tile_occupancy(L, TRO, sizeof(typename TileArith<T>::type))) idwt2_tile_kernel(const Idwt2TileArgs<T, L> a) {

@@ -1,4 +1,4 @@
-// mifwt_idwt2_tile_long_a.hip — LDS-tile 2-D synthesis kernel (mifwt_idwt2_tile.h): 18- and 20-tap filters, f32 / f16.
+// mifwt_idwt2_tile_long_a.hip — LDS-tile 2-D synthesis kernel (mifwt_idwt2_tile.h): 18- and 20-tap filters, f32 / f16 / bf16.
 #include "mifwt_idwt2_tile.h"
 
 namespace mifwt {
@@ -7,9 +7,11 @@ int idwt2_tile_long_a(const mifwt_level_desc* d, const void* approx, const void*
                           LevelTaps t, hipStream_t stream) {
   switch (d->filt_len) {
     case 18:
+      if (d->dtype == MIFWT_BF16) return launch_idwt_tr<__bf16, 18>(d, approx, details, y, t, stream);
       return d->dtype == MIFWT_F16 ? launch_idwt_tr<_Float16, 18>(d, approx, details, y, t, stream)
                                    : launch_idwt_tr<float, 18>(d, approx, details, y, t, stream);
     case 20:
+      if (d->dtype == MIFWT_BF16) return launch_idwt_tr<__bf16, 20>(d, approx, details, y, t, stream);
       return d->dtype == MIFWT_F16 ? launch_idwt_tr<_Float16, 20>(d, approx, details, y, t, stream)
                                    : launch_idwt_tr<float, 20>(d, approx, details, y, t, stream);
     default: return MIFWT_ERR_UNSUPPORTED;

@@ -410,7 +410,7 @@ int fused_check(const mifwt_level_desc* d) {
   if (!d) return MIFWT_ERR_BADARG;
   if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0)
     return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && d->dtype != MIFWT_F16) return MIFWT_ERR_BADARG;
+  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
   for (int ax = 0; ax < d->ndim; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];
     if (n < 1 || m != (n + 1) / 2) return MIFWT_ERR_BADARG;
@@ -527,7 +527,7 @@ int per_axis(int inverse, int dtype, int filt_len, int64_t outer, int64_t n, int
              void* out1, const int64_t* sig_s, const int64_t* lo_s, const int64_t* hi_s, const double* lo, const double* hi, void* stream) {
   if (!in0 || !out0 || (inverse ? !in1 : !out1) || !sig_s || !lo_s || !hi_s || !lo || !hi) return MIFWT_ERR_BADARG;
   if (filt_len < 2 || (filt_len & 1) || filt_len > MIFWT_MAX_FILT || outer < 0 || inner < 0 || n < 1) return MIFWT_ERR_BADARG;
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return dtype == MIFWT_F16 ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
+  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return is_storage16(dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
   if (n > INT32_MAX / 4) return MIFWT_ERR_UNSUPPORTED;
   AxisArgs a;
   a.in0 = in0;

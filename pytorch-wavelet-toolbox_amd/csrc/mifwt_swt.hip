@@ -185,6 +185,7 @@ int swt_level(int inverse, int dtype, int filt_len, int64_t rows, int64_t n, int
     case MIFWT_F32: return swt_dispatch<float>(c);
     case MIFWT_F64: return swt_dispatch<double>(c);
     case MIFWT_F16: return swt_dispatch<_Float16>(c);
+    case MIFWT_BF16: return swt_dispatch<__bf16>(c);
     default: return MIFWT_ERR_BADARG;
   }
 }

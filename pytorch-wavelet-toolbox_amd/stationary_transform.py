@@ -557,8 +557,8 @@ def swt2(data: torch.Tensor, wavelet: Union[Wavelet, str], level: Optional[int] 
 
     A level is the level of :func:`swt` (periodic, dilation ``2^level index``, scale 1) along both axes.  ``level=None`` means
     ``min(swt_max_level(H), swt_max_level(W))`` — odd extents give ``[data]``; as in :func:`swt` no level is refused, the periodic index
-    map wraps as often as needed.  Only float32 and float64 are accepted: float16 raises ``ValueError("Input dtype ... not
-    supported")`` even inside ``half_storage()`` (the fused kernels have no float16 form).  Differentiable w.r.t. the data to any
+    map wraps as often as needed.  Only float32 and float64 are accepted: float16 / bfloat16 raise ``ValueError("Input dtype ... not
+    supported")`` even inside ``half_storage()`` (the fused kernels have no 16-bit form).  Differentiable w.r.t. the data to any
     order; a learnable (tensor-valued) filter bank runs on the composed route and has tap gradients up to second order."""
     axes = _fwt._ensure_axes(axes, 2)
     layout = _fwt._Layout(data, 2, axes)
@@ -793,8 +793,8 @@ def swt3(data: torch.Tensor, wavelet: Union[Wavelet, str], level: Optional[int] 
 
     A level is the level of :func:`swt` (periodic, dilation ``2^level index``, scale 1) along each of the three axes.  ``level=None``
     means the minimum of ``swt_max_level`` over the three extents — odd extents give ``[data]``; as in :func:`swt` no level is refused,
-    the periodic index map wraps as often as needed.  Only float32 and float64 are accepted: float16 raises ``ValueError("Input dtype
-    ... not supported")`` even inside ``half_storage()`` (the fused kernels have no float16 form).  Differentiable w.r.t. the data to
+    the periodic index map wraps as often as needed.  Only float32 and float64 are accepted: float16 / bfloat16 raise ``ValueError("Input dtype
+    ... not supported")`` even inside ``half_storage()`` (the fused kernels have no 16-bit form).  Differentiable w.r.t. the data to
     any order; a learnable (tensor-valued) filter bank runs on the composed route and has tap gradients up to second order."""
     axes = _fwt._ensure_axes(axes, 3)
     layout = _fwt._Layout(data, 3, axes)
