@@ -554,6 +554,33 @@ int mifwt_ext_axis_adj(int ext_mode, int dtype, int filt_len, int64_t outer, int
                        const void* g_hi, const int64_t* hi_strides, void* g_x, const int64_t* x_strides, const double* lo, const double* hi,
                        void* stream);
 
+/* COMPLEX levels — the padded levels of the five index-map modes on INTERLEAVED complex data (complex64 / complex128: pairs (re, im) of
+ * float / double), as PyWavelets computes them: the taps are real, so T(a + i b) = T(a) + i T(b), band by band.  desc->dtype names the
+ * COMPONENT type, MIFWT_F32 or MIFWT_F64 (a 16-bit storage type: MIFWT_ERR_UNSUPPORTED); every extent and every stride of the descriptor
+ * counts COMPLEX elements, and so does every index below.  Per axis, L even, taps in PyWavelets order:
+ *     extension   xe[i] = x[s(i)], s the index map of desc->mode (enum mifwt_mode; zero mode: xe[i] = 0 outside) applied to the COMPLEX
+ *                 index i, any number of wraps — element i of the pad is a whole element of the signal, never a swapped pair
+ *     analysis    M = floor((N + L - 1) / 2);  cA[k] = sum_j dec_lo[j] xe[2 k + 1 - j],  cD likewise with dec_hi,  0 <= k < M
+ *     synthesis   y[n] = sum_k rec_lo[n + L - 2 - 2 k] cA[k] + rec_hi[n + L - 2 - 2 k] cD[k],  0 <= n < N, where sig_extent = N is the
+ *                 CROPPED output extent, 2 M - L + 2 or one less (anything else: MIFWT_ERR_BADARG); desc->mode is ignored
+ * N-D: the 1-D level per transformed axis, separably; band order as everywhere (bit (ndim-1-a) set <=> high-pass along axis a).
+ *   desc      sig_extent = N and coef_extent = M per axis as above; mode = enum mifwt_mode for the analysis
+ *   lo / hi   HOST taps, real, PyWavelets order: dec_lo / dec_hi for mifwt_cplx_fwd, rec_lo / rec_hi for mifwt_cplx_inv
+ * Fused kernels (ids 46 / 47, csrc/mifwt_cplx.hip): even L from 2 to 20, ndim 1 or 2, unit innermost strides, any extent >= 1: one launch
+ * per level, no workspace, no atomics (the same input gives the same bits, and the real plane of every output depends on the real plane
+ * of the input alone).  mifwt_cplx_supported / mifwt_cplx_kernel_id are decided on the host (direction 0 analysis, 1 synthesis): 1 / the
+ * kernel id where the fused kernels serve the level, 0 / MIFWT_ERR_UNSUPPORTED where they do not (ndim 3, L > 20, a non-unit innermost
+ * stride; mifwt_cplx_fwd / _inv then launch nothing and return MIFWT_ERR_UNSUPPORTED: filter the two components with the real entry
+ * points), MIFWT_ERR_BADARG for inconsistent arguments. */
+#define MIFWT_KID_CPLX_FWD 46 /* fused analysis level, ndim 1 or 2 */
+#define MIFWT_KID_CPLX_INV 47 /* fused padded synthesis level with its crop */
+int mifwt_cplx_supported(const mifwt_level_desc* desc, int direction);
+int mifwt_cplx_kernel_id(const mifwt_level_desc* desc, int direction);
+int mifwt_cplx_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* dec_lo,
+                   const double* dec_hi, void* stream);
+int mifwt_cplx_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* rec_lo,
+                   const double* rec_hi, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -615,7 +642,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   38 / 39  fused periodized analysis / synthesis level, 1-D and 2-D (mifwt_per_fwd / mifwt_per_inv; answered by mifwt_per_kernel_id)
  *   40 / 41  one axis of a periodized level through a run-time tap loop (mifwt_per_axis_fwd / mifwt_per_axis_inv)
  *   42 / 43  fused value-map extension analysis level / its adjoint, 1-D and 2-D (mifwt_ext_fwd / mifwt_ext_adj; answered by mifwt_ext_kernel_id)
- *   44 / 45  one axis of such a level / of its adjoint through a run-time tap loop (mifwt_ext_axis_fwd / mifwt_ext_axis_adj) */
+ *   44 / 45  one axis of such a level / of its adjoint through a run-time tap loop (mifwt_ext_axis_fwd / mifwt_ext_axis_adj)
+ *   46 / 47  fused analysis / padded synthesis level of interleaved complex data, 1-D and 2-D (mifwt_cplx_fwd / mifwt_cplx_inv; answered by
+ *          mifwt_cplx_kernel_id; counted under their ids by mifwt_launch_count) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

@@ -6,6 +6,11 @@ src/ptwt/__init__.py:12-19); every decomposition / reconstruction level runs as 
 for gfx950 reached through the C ABI of ``libmifwt.so`` (include/mifwt.h).  Tensors must live on a ROCm
 device; there is no CPU fallback.
 
+The ten functions take ``float32`` / ``float64`` and, as PyWavelets does, ``complex64`` / ``complex128`` data in every mode: the taps
+are real, so the two components are filtered separately, ``T(a + i b) = T(a) + i T(b)``, and the coefficients keep the input's
+complex dtype (interleaved HIP levels in the five index-map modes, ``_cplx.py``; composed from the real calls elsewhere and wherever
+a gradient is wanted).  ``swt*``, the packet trees and the ``Matrix*`` classes take real data only.
+
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
 """

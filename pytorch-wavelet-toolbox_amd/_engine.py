@@ -155,6 +155,14 @@ EXT_ENTRIES: dict = {
     "mifwt_ext_axis_adj": (_c, [_c, _c, _c, _i64, _i64, _i64, _vp, _i64_p, _vp, _i64_p, _vp, _i64_p, _dbl_p, _dbl_p, _vp]),
 }
 
+# The complex levels (_cplx.py; include/mifwt.h, mifwt_cplx_*): bound privately for the same reason.
+CPLX_ENTRIES: dict = {
+    "mifwt_cplx_supported": (_c, [_desc_p, _c]),
+    "mifwt_cplx_kernel_id": (_c, [_desc_p, _c]),
+    "mifwt_cplx_fwd": (_c, [_desc_p, _vp, _vp, _vpp, _dbl_p, _dbl_p, _vp]),
+    "mifwt_cplx_inv": (_c, [_desc_p, _vp, _vpp, _vp, _dbl_p, _dbl_p, _vp]),
+}
+
 _MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
                    "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
 _abi_mismatch = False
@@ -952,22 +960,27 @@ class HipLevelEngine:
         _enqueue(a, lib.mifwt_tap_correlate_planes, _DTYPE_IDS[a.dtype], along, a.shape[0], a.shape[1], a.shape[2], b.shape[1], b.shape[2],
                  a.data_ptr(), a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), filt_len, c0, sgn, mode_id, out.data_ptr())
 
-    def analysis_outer(self, x: torch.Tensor, dec_lo, dec_hi, mode_id: int):
+    def analysis_outer(self, x: torch.Tensor, dec_lo, dec_hi, mode_id: int, out=None):
         """One 1-D analysis level along the MIDDLE axis of ``x`` [B, N, C] (unit stride along C, any batch / row strides) ->
         ``(lo, hi)`` [B, M, C] each (planes of one [B, 2, M, C] buffer): the streaming outer-axis kernel on its own (C ABI
-        ``mifwt_dwt1_fwd_outer``); taps as host numbers or :class:`DevTaps`."""
+        ``mifwt_dwt1_fwd_outer``); taps as host numbers or :class:`DevTaps`.  ``out``: the two bands as tensors of the caller's —
+        [B, M, C] each, dense rows, one batch stride — written in place of a fresh buffer."""
         _require_gpu(x)
         lib = load_library()
         x = _unit_last(x)
         B, N, C = x.shape
         flen = len(dec_lo)
         M = (N + flen - 1) // 2
-        buf = torch.empty((B, 2, M, C), dtype=x.dtype, device=x.device)
+        if out is None:
+            buf = torch.empty((B, 2, M, C), dtype=x.dtype, device=x.device)
+            out = (buf[:, 0], buf[:, 1])
+        else:
+            assert all(t.shape == (B, M, C) and t.dtype == x.dtype and t.stride() == (out[0].stride(0), C, 1) for t in out)
         if B and N and C:
             _, dev, lo, hi = _with_taps(dec_lo, dec_hi)
-            _enqueue(x, lib.mifwt_dwt1_fwd_outer, _DTYPE_IDS[x.dtype], B, N, C, x.data_ptr(), x.stride(0), x.stride(1), buf.data_ptr(),
-                     buf.data_ptr() + M * C * x.element_size(), 2 * M * C, C, mode_id, flen, *((None, None, lo, hi) if dev else (lo, hi, None, None)))
-        return buf[:, 0], buf[:, 1]
+            _enqueue(x, lib.mifwt_dwt1_fwd_outer, _DTYPE_IDS[x.dtype], B, N, C, x.data_ptr(), x.stride(0), x.stride(1), out[0].data_ptr(),
+                     out[1].data_ptr(), out[0].stride(0), C, mode_id, flen, *((None, None, lo, hi) if dev else (lo, hi, None, None)))
+        return out[0], out[1]
 
     def synthesis_outer(self, lo: torch.Tensor, hi: torch.Tensor, rec_lo, rec_hi, n_out: int) -> torch.Tensor:
         """One 1-D synthesis level along the MIDDLE axis: ``lo``, ``hi`` [B, M, C] (unit stride along C) -> [B, n_out, C]

@@ -820,6 +820,8 @@ def _check_pad_levels(extents: Sequence[int], flen: int, mode, level: int) -> No
 
 def analysis(data: torch.Tensor, wavelet, mode, level: Optional[int], axes: AxisHint, ndim: int):
     """Multi-level analysis.  Returns ``(layout, approx [B,*M], [buffer [B,2^n,*M] per level, coarsest first])``."""
+    if _is_complex(data):  # (before every dtype check: complex64 / complex128 have a route of their own, in every mode)
+        return _analysis_cplx(data, wavelet, mode, level, axes, ndim)
     if isinstance(mode, str) and mode == PERIODIZATION:
         return _analysis_per(data, wavelet, level, axes, ndim)
     if isinstance(mode, str) and mode in EXT_MODES:
@@ -1008,6 +1010,8 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
               separable: bool, mode=None) -> torch.Tensor:
     """Multi-level synthesis.  ``levels``: per level (coarsest first) the 2^n-1 detail tensors in band order.  ``mode``: "periodization"
     selects the periodized synthesis; the padded synthesis does not depend on its mode, which is only checked."""
+    if _is_complex(approx):  # (a real approximation with complex details stays with the same-dtype check below)
+        return _synthesis_cplx(approx, levels, wavelet, axes, ndim, separable, mode)
     if isinstance(mode, str) and mode == PERIODIZATION:
         return _synthesis_per(approx, levels, wavelet, axes, ndim, separable)
     if mode is not None and not (isinstance(mode, str) and mode in EXT_MODES):
@@ -1237,6 +1241,84 @@ def _analysis_ext(data: torch.Tensor, wavelet, mode: str, level: Optional[int], 
         bufs.insert(0, buf)
         cur = buf[:, 0]
     return layout, cur, bufs
+
+
+# ------------------------------------------------------------------------------------------ complex data
+# complex64 / complex128 in every mode (include/mifwt.h, _cplx.py): the taps are real, so T(a + i b) = T(a) + i T(b), which is what
+# PyWavelets computes.  FUSED: the five index-map modes on a ROCm tensor, host taps, no graph wanted — one complex level call per trip
+# (interleaved kernels; a level outside their envelope composes itself from the two real levels).  COMPOSED: every other call is
+# torch.complex(f(x.real), f(x.imag)) with f the real call of this module, whose checks raise what they raise for real data and whose
+# autograd Functions, with torch's own real / imag / complex backward, give data gradients of any order and the tap gradients.
+def _is_complex(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype in (torch.complex64, torch.complex128)
+
+
+def _cplx_composed(wavelet, tensors: Sequence[torch.Tensor], mode) -> bool:
+    """Whether a call on complex data is composed from the real calls (see above); refuses complex taps."""
+    bank = () if isinstance(wavelet, str) else (wavelet if isinstance(wavelet, tuple) else getattr(wavelet, "filter_bank", ()))
+    if any(isinstance(t, torch.Tensor) and t.is_complex() for t in bank):
+        raise ValueError("the filter taps of a transform of complex data must be real")
+    if not (mode is None or (isinstance(mode, str) and mode in _engine.MODE_IDS)):
+        return True
+    if not all(t.is_cuda for t in tensors):
+        return True  # (the real call raises the engine's error about the ROCm device)
+    if torch.is_grad_enabled() and (_tap_tensors(wavelet) is not None or any([t.requires_grad for t in tensors])):
+        return True
+    return device_bank(wavelet, tensors[0].device) is not None or len(host_taps(wavelet)[0]) % 2 == 1
+
+
+def _analysis_cplx(data: torch.Tensor, wavelet, mode, level: Optional[int], axes: AxisHint, ndim: int):
+    from . import _cplx
+
+    if _cplx_composed(wavelet, [data], mode):
+        layout, a_re, b_re = analysis(data.real, wavelet, mode, level, axes, ndim)
+        _, a_im, b_im = analysis(data.imag, wavelet, mode, level, axes, ndim)
+        return layout, torch.complex(a_re, a_im), [_cplx.tree_complex(r, i) for r, i in zip(b_re, b_im)]
+    axes = _ensure_axes(axes, ndim)
+    layout = _Layout(data.real, ndim, axes)  # (the float view: a layout holds shapes and the permutation only)
+    x = layout.fold(data)
+    dec_lo, dec_hi, _, _ = host_taps(wavelet)
+    flen = len(dec_lo)
+    if level is None:
+        level = dwtn_max_level(x.shape[1:], flen)
+    mode_id = _mode_id(mode)
+    _check_pad_levels(x.shape[1:], flen, mode, level)
+    bufs: list = []  # coarsest level first
+    cur = x
+    for _ in range(level):
+        buf = _cplx.level_fwd(cur, dec_lo, dec_hi, mode_id)
+        bufs.insert(0, buf)
+        cur = buf[:, 0]
+    return layout, cur, bufs
+
+
+def _synthesis_cplx(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, axes: AxisHint, ndim: int, separable: bool,
+                    mode) -> torch.Tensor:
+    from . import _cplx
+
+    flat = [approx] + [t for lvl in levels for t in lvl]
+    for t in flat:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"Unexpected input type {type(t)}")
+    _check_same_device_dtype(flat)  # (a container that mixes real and complex tensors: the same-dtype error)
+    if _cplx_composed(wavelet, flat, mode):
+        parts = [synthesis(part(approx), [[part(t) for t in lvl] for lvl in levels], wavelet, axes, ndim, separable, mode)
+                 for part in (torch.real, torch.imag)]
+        return torch.complex(*parts)
+    axes = _ensure_axes(axes, ndim)
+    layout = _Layout(approx.real, ndim, axes)
+    _, _, rec_lo, rec_hi = host_taps(wavelet)
+    flen = len(rec_lo)
+    cur = layout.fold(approx)
+    folded = [[layout.fold(t) for t in lvl] for lvl in levels]
+    exts, err = _walk_synthesis(tuple(cur.shape), folded, flen, ndim, separable)
+    for pos, det in enumerate(folded):
+        if separable:
+            cur = cur[tuple(slice(0, s_) for s_ in det[0].shape)]
+        if pos == len(exts):
+            raise err
+        cur = _cplx.level_inv([cur, *det], rec_lo, rec_hi, exts[pos])
+    return layout.unfold(cur)
 
 
 # ------------------------------------------------------------------------------------------ containers

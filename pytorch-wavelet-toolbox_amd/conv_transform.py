@@ -17,7 +17,8 @@ def wavedec(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: ExtendedB
 
     Drop-in for ``ptwt.wavedec`` (src/ptwt/conv_transform.py:69-143): same arguments, defaults, container,
     coefficient lengths ``floor((N + L - 1) / 2)`` per level and error types.  Every level is one fused HIP
-    kernel (boundary extension by index map + both filters), never a padded copy.
+    kernel (boundary extension by index map + both filters), never a padded copy.  ``complex64`` / ``complex128`` data: each component
+    is transformed with the real taps, the coefficients are complex (``_fwt._analysis_cplx``).
     """
     layout, approx, bufs = _fwt.analysis(data, wavelet, mode, level, axis, 1)
     return _fwt.pack_1d(layout, approx, bufs)
@@ -27,7 +28,8 @@ def waverec(coeffs: Sequence[torch.Tensor], wavelet: Union[Wavelet, str], *, axi
             mode: Optional[ExtendedBoundaryMode] = None) -> torch.Tensor:
     """Inverse of :func:`wavedec` (src/ptwt/conv_transform.py:146-204); odd-length inputs come back one
     sample longer, exactly as in the reference.  ``mode``: ``"periodization"`` inverts a periodized decomposition; None or a padded
-    mode is the padded synthesis, which does not depend on the mode."""
+    mode is the padded synthesis, which does not depend on the mode.  Complex coefficients (all of one complex dtype) give the complex
+    signal."""
     if not isinstance(coeffs, list):
         coeffs = list(coeffs)
     if not coeffs or not isinstance(coeffs[0], torch.Tensor):

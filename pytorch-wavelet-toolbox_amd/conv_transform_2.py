@@ -17,7 +17,8 @@ def wavedec2(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: Extended
 
     Drop-in for ``ptwt.wavedec2`` (src/ptwt/conv_transform_2.py:74-157).  The reference's dense
     ``[4,1,L,L]`` conv2d is an outer product of the 1-D pair (src/ptwt/_util.py:886-907); the engine
-    computes the same four bands separably in one fused kernel per level.
+    computes the same four bands separably in one fused kernel per level.  ``complex64`` / ``complex128`` data: each
+    component is transformed with the real taps, the coefficients are complex.
     """
     layout, approx, bufs = _fwt.analysis(data, wavelet, mode, level, axes, 2)
     return _fwt.pack_2d(layout, approx, bufs)
@@ -26,7 +27,8 @@ def wavedec2(data: torch.Tensor, wavelet: Union[Wavelet, str], *, mode: Extended
 def waverec2(coeffs: WaveletCoeff2d, wavelet: Union[Wavelet, str], *, axes: _fwt.AxisHint = None,
              mode: Optional[ExtendedBoundaryMode] = None) -> torch.Tensor:
     """Inverse of :func:`wavedec2` (src/ptwt/conv_transform_2.py:160-253).  ``mode``: ``"periodization"`` inverts a periodized
-    decomposition; None or a padded mode is the padded synthesis, which does not depend on the mode."""
+    decomposition; None or a padded mode is the padded synthesis, which does not depend on the mode.  Complex coefficients (all of one
+    complex dtype) give the complex signal."""
     if len(coeffs) == 0 or not isinstance(coeffs[0], torch.Tensor):
         raise ValueError("First element of coeffs must be the approximation coefficient tensor.")
     levels = []

@@ -4,7 +4,8 @@ src/ptwt/separable_conv_transform.py:187-446).
 In the reference these run 3 (2-D) or 7 (3-D) single-axis ``wavedec`` calls per level with transposes in
 between; numerically they equal ``wavedec2`` / ``wavedec3`` (the N-D filters are outer products of the 1-D
 pair) and differ only in the return container and in how synthesis handles odd extents.  Here both API
-families share the same fused per-level kernel.
+families share the same fused per-level kernel.  All four functions take ``complex64`` / ``complex128`` tensors as well: the real
+taps filter each component, the results keep the complex dtype.
 """
 from __future__ import annotations
 
