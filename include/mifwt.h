@@ -581,6 +581,56 @@ int mifwt_cplx_fwd(const mifwt_level_desc* desc, const void* x, void* approx, vo
 int mifwt_cplx_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* rec_lo,
                    const double* rec_hi, void* stream);
 
+/* THRESHOLDING — pywt.threshold / pywt.threshold_firm over up to mifwt_thresh_max_segments() tensors per launch (csrc/mifwt_thresh.hip).
+ * With m = |x| (complex data: the magnitude of the complex number), v the threshold, s the substitute:
+ *     MIFWT_THRESH_SOFT     x max(1 - v / m, 0)         (s where m < v, if s != 0)
+ *     MIFWT_THRESH_HARD     x if m >= v, else s
+ *     MIFWT_THRESH_GARROTE  x max(1 - v^2 / m^2, 0)     (s where m < v, if s != 0)
+ *     MIFWT_THRESH_GREATER  x if x >= v, else s         (real data)
+ *     MIFWT_THRESH_LESS     x if x <= v, else s         (real data)
+ *     MIFWT_THRESH_FIRM     0 for m <= v_lo;  x v_hi (1 - v_lo / m) / (v_hi - v_lo) for v_lo < m <= v_hi;  x for m > v_hi
+ * x = 0 gives 0 (no 0 / 0), v_hi == v_lo divides nothing.  Arithmetic in float for MIFWT_F32 / F16 / BF16, in double for MIFWT_F64; `dtype`
+ * names the COMPONENT type of complex data (`is_complex`: interleaved pairs; extents and strides count complex elements).
+ * A SEGMENT is one tensor: extent[0] x extent[1] rows of extent[2] contiguous elements (stride[2] must be 1; unused outer extents are
+ * 1).  Its thresholds are host doubles (value[k]) or, where dvalue[k] is not NULL, DEVICE float64 values read by the kernel (nothing is
+ * copied to the host: capturable): element (i0, i1, .) takes dvalue[k][(i0 * extent[1] + i1) / rows_per_value[k]], rows_per_value[k] == 0
+ * meaning one value; it must divide the number of rows, and the two of a firm call must nest.  k = 0: the threshold (firm: v_lo), k = 1:
+ * firm's v_hi.  The table is copied into the kernel arguments; no device-side table, no workspace in the forward.
+ *   mifwt_thresh_fwd  (kernel id 48) y = T(x)
+ *   mifwt_thresh_bwd  (kernel id 49, real data) y = g dT/dx from the saved input x and the upstream gradient g, and, for every segment
+ *                     and k with gvalue[k] != NULL, gvalue[k][index] = sum of g dT/dv_k over the elements of that index, summed over ALL
+ *                     segments of the call that name the same gvalue[k] (hard / greater / less: nothing is written, the gradient is 0).
+ *                     `workspace`: 16 bytes per unit of mifwt_thresh_plan (float64 partials, one plain store per workgroup and
+ *                     threshold, summed per destination by a second small launch in a fixed order: no atomics, reproducible).
+ *   mifwt_thresh_plan (host only) the number of units (workgroup iterations) of the call, and, if unit_start is not NULL, the first unit
+ *                     of every segment in unit_start[0 .. nseg] (unit_start[nseg] = the total) — workspace sizing and tests.
+ * MIFWT_ERR_BADARG for nseg outside [1, mifwt_thresh_max_segments()], an unknown mode or dtype, a non-unit innermost stride, inconsistent
+ * rows_per_value; MIFWT_ERR_UNSUPPORTED for greater / less on complex data, complex 16-bit storage, extents beyond the kernels' index
+ * range (2^30 elements per row, 2^31 rows or units); MIFWT_ERR_WORKSPACE for a workspace that is too small.  Nothing is launched then. */
+#define MIFWT_THRESH_SOFT 0
+#define MIFWT_THRESH_HARD 1
+#define MIFWT_THRESH_GARROTE 2
+#define MIFWT_THRESH_GREATER 3
+#define MIFWT_THRESH_LESS 4
+#define MIFWT_THRESH_FIRM 5
+#define MIFWT_KID_THRESH_FWD 48 /* thresholding, every segment of the call in one launch */
+#define MIFWT_KID_THRESH_BWD 49 /* its backward: g dT/dx and the per-workgroup partials of g dT/dv */
+typedef struct mifwt_thresh_seg {
+  const void* x;
+  void* y;
+  const void* g; /* backward only */
+  int64_t extent[3];
+  int64_t x_stride[3], y_stride[3], g_stride[3]; /* in elements */
+  double value[2];
+  const double* dvalue[2];
+  int64_t rows_per_value[2];
+  double* gvalue[2]; /* backward only */
+} mifwt_thresh_seg;
+int mifwt_thresh_max_segments(void);
+int64_t mifwt_thresh_plan(int dtype, int is_complex, const mifwt_thresh_seg* segs, int nseg, int64_t* unit_start);
+int mifwt_thresh_fwd(int dtype, int is_complex, int mode, double substitute, const mifwt_thresh_seg* segs, int nseg, void* stream);
+int mifwt_thresh_bwd(int dtype, int mode, const mifwt_thresh_seg* segs, int nseg, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -644,7 +694,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   42 / 43  fused value-map extension analysis level / its adjoint, 1-D and 2-D (mifwt_ext_fwd / mifwt_ext_adj; answered by mifwt_ext_kernel_id)
  *   44 / 45  one axis of such a level / of its adjoint through a run-time tap loop (mifwt_ext_axis_fwd / mifwt_ext_axis_adj)
  *   46 / 47  fused analysis / padded synthesis level of interleaved complex data, 1-D and 2-D (mifwt_cplx_fwd / mifwt_cplx_inv; answered by
- *          mifwt_cplx_kernel_id; counted under their ids by mifwt_launch_count) */
+ *          mifwt_cplx_kernel_id; counted under their ids by mifwt_launch_count)
+ *   48 / 49  thresholding of up to mifwt_thresh_max_segments() tensors per launch / its backward (mifwt_thresh_fwd / mifwt_thresh_bwd;
+ *          never returned by mifwt_kernel_id; counted under their ids by mifwt_launch_count) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

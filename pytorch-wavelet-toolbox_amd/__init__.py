@@ -11,6 +11,9 @@ are real, so the two components are filtered separately, ``T(a + i b) = T(a) + i
 complex dtype (interleaved HIP levels in the five index-map modes, ``_cplx.py``; composed from the real calls elsewhere and wherever
 a gradient is wanted).  ``swt*``, the packet trees and the ``Matrix*`` classes take real data only.
 
+``threshold`` / ``threshold_firm`` (``pywt.threshold`` / ``pywt.threshold_firm``) shrink a tensor or a whole coefficient container in one
+HIP launch (``thresholding.py``).
+
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
 """
@@ -36,6 +39,7 @@ from .matmul_transform_3 import MatrixWavedec3, MatrixWaverec3
 from .separable_conv_transform import fswavedec2, fswavedec3, fswaverec2, fswaverec3
 from .graphs import CapturedCall, capture
 from ._wavelets import set_device_taps
+from .thresholding import threshold, threshold_firm
 
 __version__ = "0.1.0"
 
@@ -76,4 +80,6 @@ __all__ = [
     "MatrixWaverec3",
     "capture",
     "CapturedCall",
+    "threshold",
+    "threshold_firm",
 ]
