@@ -740,6 +740,9 @@ int mifwt_pyr_profile_buffer(void* device_buffer);
 #define MIFWT_KERNEL_SWT2_INV 35       /* id 35: fused 2-D stationary synthesis level (mifwt_swt2_inv) */
 #define MIFWT_KERNEL_SWT3_FWD 36       /* id 36: fused 3-D stationary analysis level (mifwt_swt3_fwd) */
 #define MIFWT_KERNEL_SWT3_INV 37       /* id 37: fused 3-D stationary synthesis level (mifwt_swt3_inv) */
+#define MIFWT_VARIANT_TAPCORR_ROWS 50   /* tap-gradient correlation along contiguous rows: a wave per (row, 64-coefficient chunk) task */
+#define MIFWT_VARIANT_TAPCORR_COLS 51   /* ... along the rows of planes: a wave per (image, row chunk, 64-column strip) task */
+#define MIFWT_VARIANT_TAPCORR_TERM 52   /* ... one thread per term in a 64-bit loop: dilated, long, or more than 2^31 wave tasks */
 #define MIFWT_LAUNCH_COUNTERS 64
 unsigned long long mifwt_launch_count(int variant);
 

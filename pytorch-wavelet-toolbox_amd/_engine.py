@@ -280,6 +280,7 @@ MAX_PYRAMID_LEVELS = 8  # mifwt_dwt2_fwd_pyramid: three for the streaming kernel
 
 
 VARIANT_FWD_MFMA_WALK, VARIANT_FWD_MFMA_TILE, VARIANT_FWD_PYR_ST16, VARIANT_FWD_PYR_ST8 = 0, 1, 2, 3
+VARIANT_TAPCORR_ROWS, VARIANT_TAPCORR_COLS, VARIANT_TAPCORR_TERM = 50, 51, 52  # the tap-gradient correlations, by kernel (include/mifwt.h)
 
 
 def launch_count(variant: int) -> int:

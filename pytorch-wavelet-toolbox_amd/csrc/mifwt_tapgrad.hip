@@ -223,7 +223,9 @@ int tap_correlate_rows(int64_t batch, int64_t rows_per_batch, int64_t m_len, int
   else if (L <= 16) MIFWT_TC_LAUNCH(16);
   else MIFWT_TC_LAUNCH(32);
 #undef MIFWT_TC_LAUNCH
-  return hipGetLastError() == hipSuccess ? MIFWT_OK : MIFWT_ERR_LAUNCH;
+  if (hipGetLastError() != hipSuccess) return MIFWT_ERR_LAUNCH;
+  count_launch(MIFWT_VARIANT_TAPCORR_ROWS);
+  return MIFWT_OK;
 }
 
 int tap_correlate(int dtype, int64_t rows, int64_t m_len, int64_t n_len, const void* a, int64_t a_row_stride, const void* b,
@@ -256,6 +258,7 @@ int tap_correlate(int dtype, int64_t rows, int64_t m_len, int64_t n_len, const v
     else
       return MIFWT_ERR_UNSUPPORTED;
     if (hipGetLastError() != hipSuccess) return MIFWT_ERR_LAUNCH;
+    count_launch(MIFWT_VARIANT_TAPCORR_TERM);
   }
   return MIFWT_OK;
 }
@@ -300,7 +303,9 @@ int tap_correlate_cols(int64_t batch, int64_t m_len, int64_t n_len, int64_t ncol
   else if (L <= 16) MIFWT_TCC_LAUNCH(16);
   else MIFWT_TCC_LAUNCH(32);
 #undef MIFWT_TCC_LAUNCH
-  return hipGetLastError() == hipSuccess ? MIFWT_OK : MIFWT_ERR_LAUNCH;
+  if (hipGetLastError() != hipSuccess) return MIFWT_ERR_LAUNCH;
+  count_launch(MIFWT_VARIANT_TAPCORR_COLS);
+  return MIFWT_OK;
 }
 }  // namespace
 }  // namespace mifwt

@@ -28,6 +28,11 @@ mapping ``pywt.threshold`` over the container does.  Threshold tensors are read 
 to the host, nothing synchronises, a call can be captured (``ptwt_amd.capture``) and sees the values the tensor holds at replay time.
 Tensor thresholds are therefore not checked for sign or order.
 
+Size: a kernel row holds at most 2^30 elements and a tensor fewer than 2^31 rows.  A dense tensor beyond 2^30 elements, whose axes
+would merge into one longer row, is cut back into equal rows that respect the thresholds' leading axes (``_split_row``); only a tensor
+with no such cut — a single axis of a length above 2^30 without a divisor in [n / 2^30, 2^16], or one that already needs all three
+extents — is composed from torch operations (:func:`_composed`) instead.
+
 Gradients: first order w.r.t. real data and threshold tensors runs on the backward kernel (``d/dx`` and, per threshold index, the sum of
 ``g dT/dv``: float32 runs of at most 16 terms per thread, float64 from there on, no atomics).  ``hard`` / ``greater`` / ``less`` give the
 thresholds a zero gradient; ``substitute`` gets none.  While the backward itself is recorded (``create_graph=True``), and for complex
@@ -37,6 +42,7 @@ order exist there.
 from __future__ import annotations
 
 import ctypes
+import functools
 import numbers
 from typing import List, Optional, Sequence, Tuple
 
@@ -101,31 +107,34 @@ _engine._routing_caches.append(_plans)
 
 
 # ---- containers ------------------------------------------------------------------------------------------------------------------
+def _walk(obj, entry: int, leaves: List[torch.Tensor], owner: List[int]) -> None:
+    """(A module-level function, not a closure of :func:`_flatten`: a nested function that calls itself is a reference cycle, and one
+    that also closes over ``leaves`` kept every input tensor of a call alive until the cyclic collector ran — a batch of 8 GiB stayed
+    allocated after ``threshold`` had returned and its caller had dropped it.)"""
+    if isinstance(obj, torch.Tensor):
+        leaves.append(obj)
+        owner.append(entry)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            _walk(v, entry, leaves, owner)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _walk(v, entry, leaves, owner)
+    else:
+        raise TypeError(f"threshold: a coefficient container holds tensors, tuples and dicts of tensors, not {type(obj).__name__}")
+
+
 def _flatten(data) -> Tuple[List[torch.Tensor], List[int], int]:
     """(the tensors of a container in order, the container entry each belongs to, the number of entries); a tensor is one entry."""
     leaves: List[torch.Tensor] = []
     owner: List[int] = []
-
-    def walk(obj, entry):
-        if isinstance(obj, torch.Tensor):
-            leaves.append(obj)
-            owner.append(entry)
-        elif isinstance(obj, dict):
-            for v in obj.values():
-                walk(v, entry)
-        elif isinstance(obj, (list, tuple)):
-            for v in obj:
-                walk(v, entry)
-        else:
-            raise TypeError(f"threshold: a coefficient container holds tensors, tuples and dicts of tensors, not {type(obj).__name__}")
-
     if isinstance(data, torch.Tensor):
-        walk(data, 0)
+        _walk(data, 0, leaves, owner)
         return leaves, owner, 1
     if not isinstance(data, (list, tuple)):
         raise TypeError(f"threshold: expected a tensor or a coefficient container, got {type(data).__name__}")
     for i, e in enumerate(data):
-        walk(e, i)
+        _walk(e, i, leaves, owner)
     return leaves, owner, len(data)
 
 
@@ -186,11 +195,41 @@ def _lead(v, t: torch.Tensor) -> int:
 
 
 # ---- geometry --------------------------------------------------------------------------------------------------------------------
+#: what ``seg_geometry`` of csrc/mifwt_thresh.hip takes: rows of at most 2^30 elements, an inner row extent of at most 2^30, fewer
+#: than 2^31 rows
+ROW_LIMIT = 1 << 30
+_ROWS_LIMIT = 1 << 31
+
+
+#: how many rows :func:`_split_row` tries: the search is host work, a modulo per candidate.  Rows get shorter as their number grows and
+#: the kernel does not mind, but a length whose smallest divisor from ``ceil(n / ROW_LIMIT)`` on lies beyond this (3 x a prime above
+#: 2^30) is treated as having none and takes the composed route, whose temporaries are several times the tensor.
+SPLIT_SEARCH = 1 << 16
+
+
+def _split_row(n: int):
+    """A dense row of ``n > ROW_LIMIT`` elements as ``(a, b)``: ``a`` rows of ``b <= ROW_LIMIT`` elements with the longest such ``b``
+    (the smallest divisor ``a`` of ``n`` from ``ceil(n / ROW_LIMIT)`` on, up to SPLIT_SEARCH rows), or None where ``n`` has none."""
+    a = -(-n // ROW_LIMIT)
+    while a <= SPLIT_SEARCH:
+        if n % a == 0:
+            return a, n // a
+        a += 1
+    return None
+
+
+def _kernel_takes(t: torch.Tensor, leads: Tuple[int, int]) -> bool:
+    """Whether the kernels take ``t``.  Anything of at most ROW_LIMIT elements is inside their envelope in every form; beyond that it is
+    what :func:`_form` says (a row that could not be cut back — a prime length, no free extent — is not)."""
+    return t.numel() <= ROW_LIMIT or _form(tuple(t.shape), tuple(t.stride()), tuple(leads)) is not None
+
+
 def _collapse(shape, stride, barriers):
     """``shape`` / ``stride`` as at most three extents with element strides, outermost first, the innermost with unit stride.  A
     ``barrier`` b says that a threshold indexes the first b axes: no extent merges axes from both of its sides, and the innermost
-    extent lies behind every barrier.  Returns (extents, strides, rows per threshold index for each barrier), or None where the
-    tensor has no such form (it is then read from a contiguous copy)."""
+    extent lies behind every barrier.  A merged innermost extent of more than ROW_LIMIT elements (a dense tensor of several GiB) is cut
+    back into rows the kernels take where an extent is free for them (:func:`_split_row`).  Returns (extents, strides, rows per
+    threshold index for each barrier), or None where the tensor has no such form (it is then read from a contiguous copy)."""
     nd = len(shape)
     dims: list = []  # [size, stride, first axis]
     for ax in range(nd):
@@ -203,6 +242,11 @@ def _collapse(shape, stride, barriers):
             dims.append([shape[ax], stride[ax], ax])
     if not dims or any(dims[-1][2] < b for b in barriers):
         dims.append([1, 1, nd])
+    if dims[-1][0] > ROW_LIMIT and dims[-1][1] == 1 and len(dims) < 3:
+        # a merged row longer than the kernels take: cut back into `a` dense rows of `b` elements (behind every barrier, as the row was)
+        cut = _split_row(dims[-1][0])
+        if cut is not None:
+            dims[-1:] = [[cut[0], cut[1], dims[-1][2]], [cut[1], 1, dims[-1][2]]]
     if (dims[-1][0] > 1 and dims[-1][1] != 1) or len(dims) > 3:
         return None
     ext = [1] * (3 - len(dims)) + [d[0] for d in dims]
@@ -217,17 +261,32 @@ def _collapse(shape, stride, barriers):
     return ext, st, rows_per
 
 
-def _geometry(t: torch.Tensor, leads: Tuple[int, int]):
-    """The collapsed form of ``t`` for thresholds that index ``leads`` leading axes (0: one value): (the tensor to read — ``t`` or a
-    contiguous copy —, extents, strides, rows per threshold index (0: one value) for each of the two thresholds)."""
+@functools.lru_cache(maxsize=1024)
+def _form(shape: Tuple[int, ...], stride: Tuple[int, ...], leads: Tuple[int, int]):
+    """The collapsed form of a tensor of ``shape`` / ``stride`` for thresholds that index ``leads`` leading axes (0: one value): (whether
+    it is read from a contiguous copy, extents, strides, rows per threshold index (0: one value) for each of the two thresholds) — or
+    None where that form is outside the kernels' envelope (ROW_LIMIT, _ROWS_LIMIT).  Pure and cached: the one place that decides both."""
     barriers = sorted({b for b in leads if b > 0})
-    g = _collapse(tuple(t.shape), tuple(t.stride()), barriers)
+    g, copy = _collapse(shape, stride, barriers), False
     if g is None:
-        t = t.contiguous()
-        g = _collapse(tuple(t.shape), tuple(t.stride()), barriers)
+        dense, run = [], 1
+        for n in reversed(shape):
+            dense.insert(0, run)
+            run *= n
+        g, copy = _collapse(shape, tuple(dense), barriers), True
     ext, st, rp = g
+    if ext[2] > ROW_LIMIT or ext[1] > ROW_LIMIT or ext[0] * ext[1] >= _ROWS_LIMIT:
+        return None
     rows = dict(zip(barriers, rp))
-    return t, ext, st, [rows[b] if b > 0 else 0 for b in leads]
+    return copy, tuple(ext), tuple(st), tuple(rows[b] if b > 0 else 0 for b in leads)
+
+
+def _geometry(t: torch.Tensor, leads: Tuple[int, int]):
+    """:func:`_form` of ``t`` with the tensor to read in front — ``t`` or a contiguous copy —, or None outside the envelope."""
+    form = _form(tuple(t.shape), tuple(t.stride()), tuple(leads))
+    if form is None:
+        return None
+    return (t.contiguous() if form[0] else t, *form[1:])
 
 
 def _dense_strides(ext):
@@ -359,7 +418,7 @@ def _build_recipe(xs, los, his, gs) -> _Recipe:
                 if not g.is_contiguous():
                     leads = (_lead(los[i], g), _lead(his[i], g) if his is not None else 0)
                     cg = _collapse(tuple(g.shape), tuple(g.stride()), sorted({b for b in leads if b > 0}))
-                    if cg is not None and cg[0] == ext:
+                    if cg is not None and tuple(cg[0]) == tuple(ext):
                         gst = cg[1]
                     else:
                         r.copy_g.append(i)
@@ -558,7 +617,8 @@ def _apply(data, lo, hi, mode: int, sub: float):
             raise ValueError("threshold: modes 'greater' and 'less' are defined for real data only")
     for t in leaves:
         _engine._require_gpu(t)
-    # the tensors that run: not spared by a None entry, not empty; grouped by (dtype, device), a launch sequence each
+    # the tensors that run: not spared by a None entry, not empty; a tensor beyond the kernels' envelope whose rows cannot be cut back
+    # into it (module docstring) is composed here and now; the others are grouped by (dtype, device), a launch sequence each
     outs: List[Optional[torch.Tensor]] = list(leaves)
     work: dict = {}
     for i, (t, e) in enumerate(zip(leaves, owner)):
@@ -566,6 +626,10 @@ def _apply(data, lo, hi, mode: int, sub: float):
             continue
         if t.numel() == 0:
             outs[i] = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+            continue
+        lo_t, hi_t = los_e[e], None if his_e is None else his_e[e]
+        if not _kernel_takes(t, (_lead(lo_t, t), _lead(hi_t, t) if his_e is not None else 0)):
+            outs[i] = _composed(t, lo_t, hi_t, mode, sub)
             continue
         work.setdefault((t.dtype, t.device), []).append(i)
     for (dtype, _), idx in work.items():

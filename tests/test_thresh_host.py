@@ -226,3 +226,49 @@ def test_collapsed_forms():
     assert c((3, 1), (1, 1), [1]) == ([1, 3, 1], [0, 1, 1], [1])  # a last axis of one element stays the row
     assert c((4, 6), (1, 4), []) is None  # a transposed view has no unit innermost stride: read from a copy
     assert c((), (), []) == ([1, 1, 1], [0, 0, 1], [])
+
+
+def test_rows_beyond_the_kernel_limit_are_cut_back():
+    """A dense tensor of more than 2^30 elements (geometry only, no memory): the merged row is cut into the fewest equal rows the
+    kernels take, the descriptor table of the cut is accepted by the library, a per-image threshold keeps its rows; a length without
+    such a cut is left as it is and reported as outside the envelope (the composed route)."""
+    c, lim = T._collapse, T.ROW_LIMIT
+    b = 131073  # 131073 x 128 x 128 = 2^31 + 2^14 elements; 131073 = 3 x 43691
+    n = b * 128 * 128
+    assert T._split_row(n) == (3, 43691 * 16384) and T._split_row(lim + 2) == (2, lim // 2 + 1)
+    assert T._split_row((1 << 31) - 1) is None  # a prime
+    assert T._split_row(3 * 1073741827) is None  # 3 x a prime above 2^30: the first divisor from 4 on is that prime
+    assert c((b, 128, 128), (16384, 128, 1), []) == ([1, 3, 43691 * 16384], [0, 43691 * 16384, 1], [])
+    assert c((b, 128, 128), (16384, 128, 1), [1]) == ([1, b, 16384], [0, 16384, 1], [1])
+    assert c((2, lim + 2), (lim + 2, 1), [1]) == ([2, 2, lim // 2 + 1], [lim + 2, lim // 2 + 1, 1], [2])  # two cut rows per threshold index
+    assert c((lim,), (1,), []) == ([1, 1, lim], [0, 0, 1], [])  # the limit itself is a row
+    assert c(((1 << 31) - 1,), (1,), []) == ([1, 1, (1 << 31) - 1], [0, 0, 1], [])
+    meta = torch.empty((b, 128, 128), device="meta")
+    assert T._kernel_takes(meta, (0, 0)) and T._kernel_takes(meta, (1, 0))
+    assert not T._kernel_takes(torch.empty(((1 << 31) - 1,), device="meta"), (0, 0))
+    assert T._kernel_takes(torch.empty((lim,), device="meta"), (0, 0))
+    for ext, want in (((1, 3, 43691 * 16384), R.seg_geometry(3, 43691 * 16384, 4)["units"]), ((1, 1, n), -2)):  # (-2: unsupported)
+        arr = _segs()
+        arr[0].extent[:] = ext
+        arr[0].x_stride[:] = arr[0].y_stride[:] = (ext[1] * ext[2], ext[2], 1)
+        assert T._lib().mifwt_thresh_plan(0, 0, arr, 1, None) == want, ext
+
+
+def test_flattening_a_container_leaves_no_reference_cycle_around_its_tensors():
+    """``_flatten`` used to walk the container with a nested function that called itself — a reference cycle that also held the list of
+    leaves, so every input tensor of a ``threshold`` call stayed alive until the cyclic collector ran (8 GiB of device memory after a
+    call on a large batch).  With the collector off, dropping the last references must free the tensors at once."""
+    import gc
+    import weakref
+
+    gc.collect()
+    gc.disable()
+    try:
+        a, b = torch.zeros(3), torch.zeros(2, 2)
+        refs = [weakref.ref(a), weakref.ref(b)]
+        leaves, owner, n = T._flatten([a, (b, {"k": a})])
+        assert [t.shape for t in leaves] == [a.shape, b.shape, a.shape] and owner == [0, 1, 1] and n == 2
+        del leaves, a, b
+        assert all(r() is None for r in refs)
+    finally:
+        gc.enable()
