@@ -10,6 +10,7 @@ import torch
 import ptwt_amd
 from ptwt_amd import _engine
 from tests import _golden as G
+from tests import _packet_ref as R
 from tests._oracle_engine import OracleLevelEngine
 
 
@@ -98,8 +99,8 @@ def test_packets_vs_reference_goldens_gpu():
 
 @pytest.mark.gpu
 def test_packet_level_is_one_launch_fp32():
-    """Full level-3 2-D tree of a batch of images: 3 launches (one per level), every node checked against level-1
-    wavedec2 calls on its parent; round trip through reconstruct()."""
+    """Full level-3 2-D tree of a batch of images: 3 launches (one per level), all 64 leaves and every inner node checked against
+    the float64 tree of tests/_packet_ref.py (not against a call of the same kernel); round trip through reconstruct()."""
     dev = torch.device("cuda:0")
     x = torch.randn(8, 256, 256, device=dev)
     _engine.level_events = []
@@ -111,8 +112,10 @@ def test_packet_level_is_one_launch_fp32():
     finally:
         _engine.level_events = None
     assert len(nodes) == 64
-    a, (h, v, d) = ptwt_amd.wavedec2(wp["hv"], "db4", mode="symmetric", level=1)
-    for key, want in (("hva", a), ("hvh", h), ("hvv", v), ("hvd", d)):
-        assert G.relerr(wp[key].cpu().numpy(), want.cpu().numpy()) < 1e-6, key
+    want = R.nodes(x.cpu().double(), "db4", "symmetric", 3, ndim=2)
+    keys = R.all_keys(3, 2, first=1)
+    assert len(keys) == 84 and set(keys) | {""} == set(wp.keys())
+    for level, (norm, _) in R.node_errors(wp, want, keys).items():
+        assert norm < 1e-6, (level, norm)
     wp.reconstruct()
     assert G.relerr(wp[""].cpu().numpy(), x.cpu().numpy()) < 2e-6
