@@ -631,6 +631,54 @@ int64_t mifwt_thresh_plan(int dtype, int is_complex, const mifwt_thresh_seg* seg
 int mifwt_thresh_fwd(int dtype, int is_complex, int mode, double substitute, const mifwt_thresh_seg* segs, int nseg, void* stream);
 int mifwt_thresh_bwd(int dtype, int mode, const mifwt_thresh_seg* segs, int nseg, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ESTIMATORS — the noise level of a detail band (median absolute deviation) and the VisuShrink / BayesShrink thresholds of a coefficient
+ * container, written on the device in the form mifwt_thresh_fwd reads (csrc/mifwt_estim.hip).  MIFWT_F32 / MIFWT_F64.
+ * A BAND is one tensor: extent[0] x extent[1] rows of extent[2] contiguous elements (stride[2] must be 1; unused outer extents are 1);
+ * rows_per_index consecutive rows form one leading index ("image"; 0: the whole band is one), and it must divide the number of rows.
+ * An image holds fewer than 2^31 elements.
+ *   mifwt_estim_sigma       per image: lo / hi = the order statistics of |x| of rank (c - 1) / 2 and c / 2 (c elements) — exact, the bits
+ *                           a sort gives, selected on the bit pattern with the sign cleared — and sigma = (lo + hi) / 2 /
+ *                           0.6744897501960817 in float64, rounded once.  order_stats ([images][2]) and sigma ([images]) are of the
+ *                           data's type, sigma64 holds the ROUNDED sigma as float64; each may be NULL.  `route` is
+ *                           MIFWT_KID_ESTIM_SELECT_LDS (50: one workgroup per image, the image's keys in LDS; at most
+ *                           mifwt_estim_lds_capacity(dtype) elements per image) or MIFWT_KID_ESTIM_SELECT_STREAM (51: digit passes over the
+ *                           band with integer counters in `workspace`, mifwt_estim_select_workspace bytes, zeroed on the stream).
+ *                           mifwt_estim_select_route names the default route (0: an empty band, nothing to launch).
+ *   mifwt_estim_stream_plan (host only) the number of digit passes of route 51 and, for a pass in range, its shift and width.
+ *   mifwt_estim_thresholds  for up to mifwt_estim_max_segments() bands that share `images`, thr[s][g] (the data's type) and thr64[s][g] (the
+ *                           rounded value as float64, what mifwt_thresh_fwd takes as dvalue); either may be NULL.
+ *                           MIFWT_ESTIM_VISU (kernel id 53): sigma64[g] * factor; the bands are not read.
+ *                           MIFWT_ESTIM_BAYES (kernel id 52): sigma^2 / sqrt(max(mean(x^2) - sigma^2, eps)), eps the machine epsilon of the
+ *                           data's type; the sums of x^2 in float64, per workgroup into `workspace` (8 bytes per unit of
+ *                           mifwt_estim_moments_plan) and per image in a fixed order by a second launch — no float atomics, reproducible.
+ *                           moments, if not NULL, receives the sums ([nseg][images]).
+ * Nothing is copied to the host and nothing synchronises: the calls can be captured.  MIFWT_ERR_BADARG for an unknown dtype, route or
+ * method, a non-unit innermost stride, inconsistent rows_per_index, bands of other image counts or an empty band in
+ * mifwt_estim_thresholds; MIFWT_ERR_UNSUPPORTED beyond the index range (2^30 elements per row, 2^31 rows, 2^31 elements per image) or the
+ * LDS capacity; MIFWT_ERR_WORKSPACE for a workspace that is too small.  The estimator launches are not counted by mifwt_launch_count. */
+#define MIFWT_KID_ESTIM_SELECT_LDS 50    /* order statistics of |x|, an image's keys resident in LDS */
+#define MIFWT_KID_ESTIM_SELECT_STREAM 51 /* order statistics of |x|, streaming digit passes with integer counters */
+#define MIFWT_KID_ESTIM_MOMENTS 52       /* sum of x^2 per (band, image) of a container + the BayesShrink thresholds */
+#define MIFWT_KID_ESTIM_VISU 53          /* the VisuShrink thresholds from sigma */
+#define MIFWT_ESTIM_VISU 0
+#define MIFWT_ESTIM_BAYES 1
+typedef struct mifwt_estim_band {
+  const void* x;
+  int64_t extent[3];
+  int64_t stride[3]; /* in elements */
+  int64_t rows_per_index;
+} mifwt_estim_band;
+int mifwt_estim_max_segments(void);
+int mifwt_estim_lds_capacity(int dtype);
+int mifwt_estim_stream_plan(int dtype, int pass, int* shift, int* width);
+int mifwt_estim_select_route(int dtype, const mifwt_estim_band* band, int force_stream);
+size_t mifwt_estim_select_workspace(int dtype, const mifwt_estim_band* band, int route);
+int mifwt_estim_sigma(int dtype, const mifwt_estim_band* band, int route, void* order_stats, void* sigma, double* sigma64, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int64_t mifwt_estim_moments_plan(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images);
+int mifwt_estim_thresholds(int dtype, int method, const mifwt_estim_band* segs, int nseg, int64_t images, const double* sigma64,
+                           double factor, void* thr, double* thr64, double* moments, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -696,7 +744,10 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   46 / 47  fused analysis / padded synthesis level of interleaved complex data, 1-D and 2-D (mifwt_cplx_fwd / mifwt_cplx_inv; answered by
  *          mifwt_cplx_kernel_id; counted under their ids by mifwt_launch_count)
  *   48 / 49  thresholding of up to mifwt_thresh_max_segments() tensors per launch / its backward (mifwt_thresh_fwd / mifwt_thresh_bwd;
- *          never returned by mifwt_kernel_id; counted under their ids by mifwt_launch_count) */
+ *          never returned by mifwt_kernel_id; counted under their ids by mifwt_launch_count)
+ *   50 / 51  exact order statistics of |x| per leading index: an image's keys in LDS / streaming digit passes (mifwt_estim_sigma;
+ *          answered by mifwt_estim_select_route)
+ *   52 / 53  sums of x^2 of a container's bands + BayesShrink thresholds / VisuShrink thresholds (mifwt_estim_thresholds) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

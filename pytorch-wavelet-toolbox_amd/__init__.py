@@ -12,7 +12,8 @@ complex dtype (interleaved HIP levels in the five index-map modes, ``_cplx.py``;
 a gradient is wanted).  ``swt*``, the packet trees and the ``Matrix*`` classes take real data only.
 
 ``threshold`` / ``threshold_firm`` (``pywt.threshold`` / ``pywt.threshold_firm``) shrink a tensor or a whole coefficient container in one
-HIP launch (``thresholding.py``).
+HIP launch (``thresholding.py``); ``estimate_sigma`` / ``estimate_thresholds`` / ``shrink`` produce the noise level and the VisuShrink /
+BayesShrink thresholds on the device and apply them (``estimators.py``).
 
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
@@ -40,6 +41,7 @@ from .separable_conv_transform import fswavedec2, fswavedec3, fswaverec2, fswave
 from .graphs import CapturedCall, capture
 from ._wavelets import set_device_taps
 from .thresholding import threshold, threshold_firm
+from .estimators import estimate_sigma, estimate_thresholds, shrink
 
 __version__ = "0.1.0"
 
@@ -82,4 +84,7 @@ __all__ = [
     "CapturedCall",
     "threshold",
     "threshold_firm",
+    "estimate_sigma",
+    "estimate_thresholds",
+    "shrink",
 ]

@@ -163,6 +163,26 @@ CPLX_ENTRIES: dict = {
     "mifwt_cplx_inv": (_c, [_desc_p, _vp, _vpp, _vp, _dbl_p, _dbl_p, _vp]),
 }
 
+
+class EstimBand(ctypes.Structure):
+    """``mifwt_estim_band``."""
+
+    _fields_ = [("x", _vp), ("extent", _i64 * 3), ("stride", _i64 * 3), ("rows_per_index", _i64)]
+
+
+# The estimators (estimators.py; include/mifwt.h, mifwt_estim_*): bound privately for the same reason.
+_band_p, _int_p = ctypes.POINTER(EstimBand), ctypes.POINTER(_c)
+ESTIM_ENTRIES: dict = {
+    "mifwt_estim_max_segments": (_c, []),
+    "mifwt_estim_lds_capacity": (_c, [_c]),
+    "mifwt_estim_stream_plan": (_c, [_c, _c, _int_p, _int_p]),
+    "mifwt_estim_select_route": (_c, [_c, _band_p, _c]),
+    "mifwt_estim_select_workspace": (_sz, [_c, _band_p, _c]),
+    "mifwt_estim_sigma": (_c, [_c, _band_p, _c, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mifwt_estim_moments_plan": (_i64, [_c, _band_p, _c, _i64]),
+    "mifwt_estim_thresholds": (_c, [_c, _c, _band_p, _c, _i64, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
                    "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
 _abi_mismatch = False
