@@ -679,6 +679,33 @@ int64_t mifwt_estim_moments_plan(int dtype, const mifwt_estim_band* segs, int ns
 int mifwt_estim_thresholds(int dtype, int method, const mifwt_estim_band* segs, int nseg, int64_t images, const double* sigma64,
                            double factor, void* thr, double* thr64, double* moments, void* workspace, size_t workspace_bytes, void* stream);
 
+/* SELECTION — the k-th largest magnitude of a coefficient container, pooled per image (csrc/mifwt_select.hip): what keeps the k largest
+ * coefficients of every image when mifwt_thresh_fwd reads it as a threshold.  MIFWT_F32 / MIFWT_F64.  `segs` are bands as above that
+ * share `images`; per image all their elements form one multiset of n magnitudes (empty bands are skipped; n < 2^31).
+ *   mifwt_select_kth        value[g] = s[n - k], s the ascending sort of |x| of image g: exact, the bits a sort gives, selected on the
+ *                           bit pattern with the sign cleared.  k = 0 gives +inf.  k is the argument (0 <= k <= n) or, where dk is not
+ *                           NULL, dk[g * dk_stride] (dk_stride 1, or 0: one k for all images), read on the device when the kernel runs
+ *                           and clipped to [0, n] there.  value ([images], the data's type) and value64 (the same values as float64,
+ *                           what mifwt_thresh_fwd takes as dvalue) may each be NULL.  `route` is MIFWT_KID_SELECT_KTH_LDS (54: one
+ *                           workgroup per image, the keys of all segments in LDS; at most mifwt_select_max_segments() non-empty
+ *                           segments and mifwt_estim_lds_capacity(dtype) pooled elements per image) or MIFWT_KID_SELECT_KTH_STREAM (55:
+ *                           the digit passes of mifwt_estim_stream_plan over all segments with integer counters in `workspace`,
+ *                           mifwt_select_workspace bytes, zeroed on the stream; any number of segments, mifwt_select_max_segments()
+ *                           per launch, several launches of a pass adding into the same counters).  NaNs are unspecified.
+ *   mifwt_select_route      (host only) the default route; 0: nothing to launch (no image or an empty pool).
+ * Nothing is copied to the host and nothing synchronises: the calls can be captured.  Integer counters only: the same input gives the
+ * same bits.  MIFWT_ERR_BADARG for an unknown dtype or route, a band mifwt_estim_* would refuse, bands of other image counts, k outside
+ * [0, n]; MIFWT_ERR_UNSUPPORTED beyond the index range (2^31 pooled elements per image) or, for route 54, its capacity;
+ * MIFWT_ERR_WORKSPACE for a workspace that is too small.  These launches are not counted by mifwt_launch_count. */
+#define MIFWT_KID_SELECT_KTH_LDS 54    /* k-th largest |x| of a container per image, the image's keys resident in LDS */
+#define MIFWT_KID_SELECT_KTH_STREAM 55 /* k-th largest |x| of a container per image, streaming digit passes with integer counters */
+int mifwt_select_max_segments(void);
+int mifwt_select_route(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, int force_stream);
+size_t mifwt_select_workspace(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, int route);
+int mifwt_select_kth(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, int64_t k, const int64_t* dk,
+                     int64_t dk_stride /* 0: one k for all images */, int route, void* value, double* value64, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -747,7 +774,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          never returned by mifwt_kernel_id; counted under their ids by mifwt_launch_count)
  *   50 / 51  exact order statistics of |x| per leading index: an image's keys in LDS / streaming digit passes (mifwt_estim_sigma;
  *          answered by mifwt_estim_select_route)
- *   52 / 53  sums of x^2 of a container's bands + BayesShrink thresholds / VisuShrink thresholds (mifwt_estim_thresholds) */
+ *   52 / 53  sums of x^2 of a container's bands + BayesShrink thresholds / VisuShrink thresholds (mifwt_estim_thresholds)
+ *   54 / 55  the k-th largest |x| of a container pooled per leading index: the keys in LDS / streaming digit passes (mifwt_select_kth;
+ *          answered by mifwt_select_route) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

@@ -13,7 +13,8 @@ a gradient is wanted).  ``swt*``, the packet trees and the ``Matrix*`` classes t
 
 ``threshold`` / ``threshold_firm`` (``pywt.threshold`` / ``pywt.threshold_firm``) shrink a tensor or a whole coefficient container in one
 HIP launch (``thresholding.py``); ``estimate_sigma`` / ``estimate_thresholds`` / ``shrink`` produce the noise level and the VisuShrink /
-BayesShrink thresholds on the device and apply them (``estimators.py``).
+BayesShrink thresholds on the device and apply them (``estimators.py``); ``keep_threshold`` / ``sparsify`` find the k-th largest magnitude
+of every image over a whole container — an exact radix selection on the device — and keep the ``k`` largest coefficients (``sparsify.py``).
 
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
@@ -42,6 +43,7 @@ from .graphs import CapturedCall, capture
 from ._wavelets import set_device_taps
 from .thresholding import threshold, threshold_firm
 from .estimators import estimate_sigma, estimate_thresholds, shrink
+from .sparsify import keep_threshold, sparsify
 
 __version__ = "0.1.0"
 
@@ -87,4 +89,6 @@ __all__ = [
     "estimate_sigma",
     "estimate_thresholds",
     "shrink",
+    "keep_threshold",
+    "sparsify",
 ]
