@@ -706,6 +706,41 @@ int mifwt_select_kth(int dtype, const mifwt_estim_band* segs, int nseg, int64_t 
                      int64_t dk_stride /* 0: one k for all images */, int route, void* value, double* value64, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* COMPACTION — the k kept coefficients of every image of a container as (values, ascending flat indices), and back
+ * (csrc/mifwt_compact.hip).  MIFWT_F32 / MIFWT_F64.  `segs` are bands as above that share `images`; the FLAT INDEX of a pooled element is
+ * its position in the image's pool: the non-empty segments in order, inside a segment the row-major index of the element within its
+ * image.  With key(x) the bit pattern of x with the sign cleared, v = value[g] the k-th largest magnitude of image g
+ * (mifwt_select_kth with the same k) and E = k - #{key > key(v)}, the element of flat index i is kept iff
+ *         key(x_i) > key(v)   or   ( key(x_i) == key(v)  and  #{ j < i : key(x_j) == key(v) } < E ):
+ * every greater element and the first E ties in flat-index order, exactly k elements; with k = 0, none.
+ *   mifwt_compact_encode    values[g][j] / indices[g][j], j < counts[g] = k: the kept elements (their original values) and their flat
+ *                           indices, ascending; slots counts[g] <= j < capacity hold value 0 and index -1.  k is the argument
+ *                           (0 <= k <= capacity) or, where dk is not NULL, dk[g * dk_stride] read on the device and clipped to
+ *                           [0, min(n, capacity)] there (the selection must have seen the same clipped k).  0 <= capacity <= n.
+ *                           `route` is MIFWT_KID_COMPACT_LDS (56: one workgroup per image, the values of all segments in LDS; the
+ *                           limits of route 54) or MIFWT_KID_COMPACT_STREAM (57: count per unit, scan per image, write per unit over a
+ *                           unit table in `workspace`, mifwt_compact_workspace bytes; any number of segments,
+ *                           mifwt_compact_max_segments() per count / write launch).  NaNs are unspecified.
+ *   mifwt_compact_move      (58) scatter (gather = 0): tensors[s][g][i - start_s] = values[g][j] for every j < counts[g] with
+ *                           i = indices[g][j] >= 0 inside the pool; gather (gather != 0): the other way.  tensors[s] is dense storage
+ *                           [images][sizes[s]], start_s the sum of the sizes before s.  Everything else is left as it is: a scatter
+ *                           goes into zero-filled storage, a gather into zero-filled values.  Indices outside [0, n) move nothing.
+ *   mifwt_compact_route     (host only) the default encode route; 0: nothing to launch (no image or an empty pool).
+ * Nothing is copied to the host and nothing synchronises: the calls can be captured.  No atomics: every output element has one writer,
+ * the same input gives the same bits.  Error codes as for mifwt_select_*; MIFWT_ERR_BADARG also for a capacity outside [0, n] and for
+ * NULL outputs.  These launches are not counted by mifwt_launch_count. */
+#define MIFWT_KID_COMPACT_LDS 56    /* the k kept elements of a container per image, compacted; the image's values resident in LDS */
+#define MIFWT_KID_COMPACT_STREAM 57 /* the same, streaming: count per unit, scan per image, write per unit */
+#define MIFWT_KID_COMPACT_MOVE 58   /* scatter / gather between compacted (values, indices) and dense per-tensor storage */
+int mifwt_compact_max_segments(void);
+int mifwt_compact_route(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, int force_stream);
+size_t mifwt_compact_workspace(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, int route);
+int mifwt_compact_encode(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, int64_t k, const int64_t* dk,
+                         int64_t dk_stride /* 0: one k for all images */, int64_t capacity, int route, const void* value, void* values,
+                         int32_t* indices, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int mifwt_compact_move(int dtype, int gather, void* const* tensors, const int64_t* sizes, int nseg, int64_t images, int64_t capacity,
+                       void* values, const int32_t* indices, const int32_t* counts, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -776,7 +811,10 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          answered by mifwt_estim_select_route)
  *   52 / 53  sums of x^2 of a container's bands + BayesShrink thresholds / VisuShrink thresholds (mifwt_estim_thresholds)
  *   54 / 55  the k-th largest |x| of a container pooled per leading index: the keys in LDS / streaming digit passes (mifwt_select_kth;
- *          answered by mifwt_select_route) */
+ *          answered by mifwt_select_route)
+ *   56 / 57  the k kept elements of a container per leading index as (values, ascending flat indices): the values in LDS / streaming
+ *          count, scan and write (mifwt_compact_encode; answered by mifwt_compact_route)
+ *   58     scatter / gather between compacted (values, indices) and dense per-tensor storage (mifwt_compact_move) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

@@ -14,7 +14,8 @@ a gradient is wanted).  ``swt*``, the packet trees and the ``Matrix*`` classes t
 ``threshold`` / ``threshold_firm`` (``pywt.threshold`` / ``pywt.threshold_firm``) shrink a tensor or a whole coefficient container in one
 HIP launch (``thresholding.py``); ``estimate_sigma`` / ``estimate_thresholds`` / ``shrink`` produce the noise level and the VisuShrink /
 BayesShrink thresholds on the device and apply them (``estimators.py``); ``keep_threshold`` / ``sparsify`` find the k-th largest magnitude
-of every image over a whole container — an exact radix selection on the device — and keep the ``k`` largest coefficients (``sparsify.py``).
+of every image over a whole container — an exact radix selection on the device — and keep the ``k`` largest coefficients (``sparsify.py``);
+``sparse_encode`` / ``sparse_decode`` compact those ``k`` survivors into ``(values, indices)`` per image and back (``sparse.py``).
 
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
@@ -44,6 +45,7 @@ from ._wavelets import set_device_taps
 from .thresholding import threshold, threshold_firm
 from .estimators import estimate_sigma, estimate_thresholds, shrink
 from .sparsify import keep_threshold, sparsify
+from .sparse import SparseCoeffs, sparse_decode, sparse_encode
 
 __version__ = "0.1.0"
 
@@ -91,4 +93,7 @@ __all__ = [
     "shrink",
     "keep_threshold",
     "sparsify",
+    "SparseCoeffs",
+    "sparse_encode",
+    "sparse_decode",
 ]

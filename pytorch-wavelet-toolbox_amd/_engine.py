@@ -191,6 +191,15 @@ SELECT_ENTRIES: dict = {
     "mifwt_select_kth": (_c, [_c, _band_p, _c, _i64, _i64, _vp, _i64, _c, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# The compaction (sparse.py; include/mifwt.h, mifwt_compact_*): bound privately for the same reason.
+COMPACT_ENTRIES: dict = {
+    "mifwt_compact_max_segments": (_c, []),
+    "mifwt_compact_route": (_c, [_c, _band_p, _c, _i64, _c]),
+    "mifwt_compact_workspace": (_sz, [_c, _band_p, _c, _i64, _c]),
+    "mifwt_compact_encode": (_c, [_c, _band_p, _c, _i64, _i64, _vp, _i64, _i64, _c, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mifwt_compact_move": (_c, [_c, _c, _vpp, _i64_p, _c, _i64, _i64, _vp, _vp, _vp, _vp]),
+}
+
 _MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
                    "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
 _abi_mismatch = False

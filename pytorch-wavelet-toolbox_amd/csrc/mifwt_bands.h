@@ -1,4 +1,5 @@
-// mifwt_bands.h — what the kernels that read coefficient BANDS share (mifwt_estim.hip, ids 50 .. 53; mifwt_select.hip, ids 54 / 55).
+// mifwt_bands.h — what the kernels that read coefficient BANDS share (mifwt_estim.hip, ids 50 .. 53; mifwt_select.hip, ids 54 / 55;
+// mifwt_compact.hip, ids 56 .. 58).
 //
 // A BAND is one strided tensor in the collapsed form of mifwt_thresh.hip: extent[0] x extent[1] rows of extent[2] contiguous elements,
 // the rows addressed through two element strides; `rows_per_index` consecutive rows form one IMAGE (one leading index).  A row is cut
@@ -9,6 +10,8 @@
 // The KEY of an element is its bit pattern with the sign cleared: for non-negative IEEE numbers unsigned order is value order, so a
 // radix selection on the keys finds an exact order statistic of |x|, the bits a sort gives.
 #pragma once
+#include <vector>
+
 #include "mifwt_common.h"
 
 namespace mifwt {
@@ -89,6 +92,20 @@ __device__ __forceinline__ void visit_slot(const Band& b, uint32_t row, uint32_t
   }
 }
 
+// where a per-image count k comes from: the number itself, or device memory read when the kernel runs
+struct KSource {
+  int64_t k;
+  const int64_t* dk;  // NULL: k
+  int64_t stride;     // 0: dk[0] for every image
+};
+
+// k of image g, clipped to [0, n]
+__device__ __forceinline__ uint32_t k_of(const KSource& s, uint32_t g, uint32_t n) {
+  int64_t k = s.dk ? s.dk[(int64_t)g * s.stride] : s.k;
+  k = k < 0 ? 0 : k;
+  return k > (int64_t)n ? n : (uint32_t)k;
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 struct Geo {
   Band b;
@@ -119,6 +136,40 @@ inline int band_geometry(int dtype, const mifwt_estim_band& s, Geo* o) {
   g.count = rp * (uint64_t)n;
   *o = g;
   return MIFWT_OK;
+}
+
+// the non-empty segments of a container whose bands share their images, one multiset per image
+struct Pool {
+  std::vector<Geo> segs;  // the non-empty segments
+  uint64_t count = 0;     // pooled elements per image
+};
+
+// the non-empty segments of a container and their pooled count; MIFWT_OK or an error code
+inline int pool_of(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, Pool* p) {
+  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return MIFWT_ERR_BADARG;
+  if (nseg < 0 || (nseg > 0 && segs == nullptr) || images < 0 || images >= 2147483648ll) return MIFWT_ERR_BADARG;
+  for (int i = 0; i < nseg; ++i) {
+    Geo g;
+    const int rc = band_geometry(dtype, segs[i], &g);
+    if (rc != MIFWT_OK) return rc;
+    if (g.count == 0) continue;
+    if (g.images != (uint64_t)images) return MIFWT_ERR_BADARG;
+    p->count += g.count;
+    if (p->count >= 2147483648ull) return MIFWT_ERR_UNSUPPORTED;  // fewer than 2^31 pooled elements per image
+    p->segs.push_back(g);
+  }
+  return MIFWT_OK;
+}
+
+// streaming: how a segment's slots are cut into units (chunks), one workgroup each: units per image, slots per unit
+inline void unit_plan(const Geo& g, uint64_t images, uint64_t* slots, uint64_t* wpi, uint64_t* spw) {
+  uint64_t per_image = kMaxWgs / images;
+  if (per_image < 1) per_image = 1;
+  *slots = (uint64_t)g.b.rp * g.b.vpr;
+  uint64_t w = (*slots + kSlotsPerWg - 1) / kSlotsPerWg;
+  if (w > per_image) w = per_image;
+  *spw = (*slots + w - 1) / w;
+  *wpi = (*slots + *spw - 1) / *spw;
 }
 
 inline int lds_capacity(int dtype) { return kLdsKeyBytes / (dtype == MIFWT_F64 ? 8 : 4); }

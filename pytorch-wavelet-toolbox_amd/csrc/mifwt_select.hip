@@ -30,19 +30,6 @@ struct KthState {
   uint32_t rank;  // its rank among the keys that share those bits
 };
 
-// where k comes from
-struct KSource {
-  int64_t k;
-  const int64_t* dk;  // NULL: k
-  int64_t stride;     // 0: dk[0] for every image
-};
-
-__device__ __forceinline__ uint32_t k_of(const KSource& s, uint32_t g, uint32_t n) {
-  int64_t k = s.dk ? s.dk[(int64_t)g * s.stride] : s.k;
-  k = k < 0 ? 0 : k;
-  return k > (int64_t)n ? n : (uint32_t)k;
-}
-
 template <typename K>
 __device__ __forceinline__ KthState<K> first_state(const KSource& s, uint32_t g, uint32_t n) {
   const uint32_t k = k_of(s, g, n);
@@ -209,6 +196,11 @@ __global__ __launch_bounds__(kThreads) void kth_stream_kernel(const KthArgs a) {
   }
 }
 
+// the counters of a pass, zeroed on the stream before the launches that fill them
+__global__ __launch_bounds__(kThreads) void zero_counters_kernel(uint32_t* counts, const size_t n) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) counts[i] = 0;
+}
+
 // after the last pass: resolve its counters, write the value.  One workgroup per image.
 template <typename C>
 __global__ __launch_bounds__(kThreads) void kth_stream_finish_kernel(const uint32_t cnt, const uint32_t images, const KSource src,
@@ -228,28 +220,6 @@ __global__ __launch_bounds__(kThreads) void kth_stream_finish_kernel(const uint3
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct Pool {
-  std::vector<Geo> segs;  // the non-empty segments
-  uint64_t count = 0;     // pooled elements per image
-};
-
-// the non-empty segments of a container and their pooled count; MIFWT_OK or an error code
-int pool_of(int dtype, const mifwt_estim_band* segs, int nseg, int64_t images, Pool* p) {
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return MIFWT_ERR_BADARG;
-  if (nseg < 0 || (nseg > 0 && segs == nullptr) || images < 0 || images >= 2147483648ll) return MIFWT_ERR_BADARG;
-  for (int i = 0; i < nseg; ++i) {
-    Geo g;
-    const int rc = band_geometry(dtype, segs[i], &g);
-    if (rc != MIFWT_OK) return rc;
-    if (g.count == 0) continue;
-    if (g.images != (uint64_t)images) return MIFWT_ERR_BADARG;
-    p->count += g.count;
-    if (p->count >= 2147483648ull) return MIFWT_ERR_UNSUPPORTED;  // fewer than 2^31 pooled elements per image
-    p->segs.push_back(g);
-  }
-  return MIFWT_OK;
-}
-
 size_t state_bytes(int dtype) { return dtype == MIFWT_F64 ? sizeof(KthState<uint64_t>) : sizeof(KthState<uint32_t>); }
 
 size_t stream_ws_bytes(int dtype, uint64_t images) {
@@ -258,16 +228,11 @@ size_t stream_ws_bytes(int dtype, uint64_t images) {
 
 // the unit table of the segments [c0, c0 + n) of the pool; the number of units
 uint64_t fill_units(const Pool& p, size_t c0, int n, uint64_t images, KthArgs* a) {
-  uint64_t per_image = kMaxWgs / images;
-  if (per_image < 1) per_image = 1;
   uint64_t total = 0;
   for (int i = 0; i < n; ++i) {
+    uint64_t slots, wpi, spw;
+    unit_plan(p.segs[c0 + i], images, &slots, &wpi, &spw);
     const Geo& g = p.segs[c0 + i];
-    const uint64_t slots = (uint64_t)g.b.rp * g.b.vpr;
-    uint64_t wpi = (slots + kSlotsPerWg - 1) / kSlotsPerWg;
-    if (wpi > per_image) wpi = per_image;
-    const uint64_t spw = (slots + wpi - 1) / wpi;
-    wpi = (slots + spw - 1) / spw;
     KSeg& s = a->seg[i];
     s.b = g.b;
     s.slots = (uint32_t)slots, s.wpi = (uint32_t)wpi, s.spw = (uint32_t)spw, s.kbase = 0;
@@ -309,7 +274,10 @@ int run_kth(const Pool& p, uint64_t images, const KSource& src, int route, void*
     a.pass = pass;
     a.counts = counters + (size_t)(pass & 1) * one;
     a.prev = counters + (size_t)((pass + 1) & 1) * one;
-    if (hipMemsetAsync(a.counts, 0, one * sizeof(uint32_t), st) != hipSuccess) return MIFWT_ERR_LAUNCH;
+    // (a kernel, not a memset: in a replayed HIP graph the counters must be zeroed strictly between the launches that read and fill them,
+    // and kernel launches of one stream keep that order among themselves)
+    hipLaunchKernelGGL(zero_counters_kernel, dim3((unsigned)std::min<size_t>((one + kThreads - 1) / kThreads, kMaxWgs)), dim3(kThreads), 0, st, a.counts, one);
+    if (hipGetLastError() != hipSuccess) return MIFWT_ERR_LAUNCH;
     for (size_t c0 = 0; c0 < p.segs.size(); c0 += kMaxSeg) {
       const uint64_t units = fill_units(p, c0, (int)std::min<size_t>(kMaxSeg, p.segs.size() - c0), images, &a);
       hipLaunchKernelGGL(kth_stream_kernel<C>, dim3((unsigned)units), dim3(kThreads), 0, st, a);
