@@ -15,6 +15,10 @@
 // the EDGE instantiation of the filter step (per-output window start and coefficient row from the table); everything else runs the
 // plain taps from registers, its window read from LDS in 16-byte pieces, without a per-element branch.
 // Everything else (20 < L <= 128, any strides) runs bwt_axis_generic: one thread per output, run-time tap loop, one axis per launch.
+// Shared with the fused levels of the other modes, from mifwt_level_tile.h (through mifwt_bwt_rows.h): the 16-byte vectors, the row pass
+// of an interior window, the tap step of the plain column pass and the band stores, the common kernel arguments and their fill, the
+// tile cut, the descriptor prelude and envelope, the length dispatch, the packing of the level entries and the axis-pass arguments and
+// launcher.  The column pass over boundary rows reads its taps from the LDS table at every use and stays here.
 #include "mifwt_bwt_rows.h"
 
 namespace mifwt {
@@ -24,7 +28,7 @@ namespace {
 // ---- tile geometry (compile time; LDS stays below the 64 KB a kernel gets without opting in) ---------------------------------------------
 template <typename T, int L>
 struct FwdTile {
-  static constexpr int E = BwtVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int TC = 16 * E;                 // coefficient columns per tile (64 f32 / 32 f64): 16 lanes x one 16-byte store
   static constexpr int TR = 8;                      // coefficient rows per tile
   static constexpr int PADI = round_up(L / 2 - 1, E);  // staged columns left of sample 2 mc0: interior tiles
@@ -38,7 +42,7 @@ struct FwdTile {
 
 template <typename T, int L>
 struct InvTile {
-  static constexpr int E = BwtVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int TQ = 16;                                            // coefficient rows per tile (32 output rows)
   static constexpr int TQC = (L <= 12 ? 16 : 8) * E;                      // coefficient columns per tile
   static constexpr int PMC = round_up(L / 2, E);                           // staged coefficients either side
@@ -50,26 +54,19 @@ struct InvTile {
   static constexpr int LDS2 = (4 * WRM * WCM + 2 * 2 * TQ * WCM + 2 * (L / 2 + 1) * L) * (int)sizeof(T);
 };
 
+// real signal extents, coefficient extents = ceil(n / 2); the filters f_lo, f_hi of the bank
 template <typename T, int L>
-struct BwtArgs {
-  const void* in[4];   // analysis: in[0] = x;  synthesis: the 2^ndim bands
-  void* out[4];        // analysis: the bands;  synthesis: out[0] = y
-  int64_t sig_bs, sig_rs;   // signal side: batch / row stride (elements; samples contiguous).  1-D: rows = batch, sig_rs unused
-  int64_t a_bs, a_rs, d_bs, d_rs;  // band 0 / bands 1..: batch / row strides
-  int batch, n_r, n_c;      // real signal extents (1-D: n_r = 1)
-  int m_r, m_c;             // coefficient extents = ceil(n / 2)
-  int src_r, src_c;         // source index of the virtual sample of an odd extent (-1: zero)
-  int sig_vec, coef_vec;    // 16-byte accesses allowed on the signal / coefficient side
-  int tiles_c, tiles_r;
-  const double* tab;        // DEVICE [2][max(nt + nb, 1)][L]
-  T lo[L], hi[L];           // f_lo, f_hi
+struct BwtArgs : LevelArgs<T, L> {
+  int batch;
+  int src_r, src_c;   // source index of the virtual sample of an odd extent (-1: zero)
+  const double* tab;  // DEVICE [2][max(nt + nb, 1)][L]
 };
 
 // ---- analysis, 2-D -----------------------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_fwd2_kernel(const BwtArgs<T, L> a) {
   typedef FwdTile<T, L> G;
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC, TR = G::TR, NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   __shared__ __attribute__((aligned(16))) T xs[G::WR * G::WC];
   __shared__ __attribute__((aligned(16))) T hs[2 * G::WR * TC];
@@ -125,15 +122,7 @@ __global__ void __launch_bounds__(256) bwt_fwd2_kernel(const BwtArgs<T, L> a) {
     if (!edge_r || (m >= NT && m < a.m_r - NB)) {
       const int w0 = 2 * ro + padr - (L / 2 - 1);
 #pragma unroll
-      for (int k = 0; k < L; ++k) {
-        const V vl = *reinterpret_cast<const V*>(hl0 + (w0 + k) * TC);
-        const V vh = *reinterpret_cast<const V*>(hh0 + (w0 + k) * TC);
-        const T cl = a.lo[L - 1 - k], ch = a.hi[L - 1 - k];
-        ll += cl * vl;
-        lh += cl * vh;
-        hl += ch * vl;
-        hh += ch * vh;
-      }
+      for (int k = 0; k < L; ++k) column_tap<T>(hl0 + (w0 + k) * TC, hh0 + (w0 + k) * TC, a.lo[L - 1 - k], a.hi[L - 1 - k], ll, lh, hl, hh);
     } else {
       int r = NR, w0 = 2 * ro + padr - (L / 2 - 1);
       if (m < NT) {
@@ -155,13 +144,7 @@ __global__ void __launch_bounds__(256) bwt_fwd2_kernel(const BwtArgs<T, L> a) {
         hh += ch[k] * vh;
       }
     }
-    const int valid = a.m_c - mc;
-    const int64_t oa = (int64_t)b * a.a_bs + (int64_t)m * a.a_rs + mc;
-    const int64_t od = (int64_t)b * a.d_bs + (int64_t)m * a.d_rs + mc;
-    store_vec<T>(static_cast<T*>(a.out[0]) + oa, ll, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[1]) + od, lh, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[2]) + od, hl, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[3]) + od, hh, valid, a.coef_vec);
+    store_bands<T, L>(a, b, m, mc, ll, lh, hl, hh);
   }
 }
 
@@ -169,7 +152,7 @@ __global__ void __launch_bounds__(256) bwt_fwd2_kernel(const BwtArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_fwd1_kernel(const BwtArgs<T, L> a) {
   typedef FwdTile<T, L> G;
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC1, NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   __shared__ __attribute__((aligned(16))) T xs[G::WC1];
   __shared__ T tl[2 * (NR + 1) * L];
@@ -200,7 +183,7 @@ __global__ void __launch_bounds__(256) bwt_fwd1_kernel(const BwtArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_inv2_kernel(const BwtArgs<T, L> a) {
   typedef InvTile<T, L> G;
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TQ = G::TQ, TQC = G::TQC, WCM = G::WCM, WRM = G::WRM, NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   __shared__ __attribute__((aligned(16))) T bs[4 * WRM * WCM];
   __shared__ __attribute__((aligned(16))) T ts[2 * 2 * TQ * WCM];
@@ -258,7 +241,7 @@ __global__ void __launch_bounds__(256) bwt_inv2_kernel(const BwtArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_inv1_kernel(const BwtArgs<T, L> a) {
   typedef InvTile<T, L> G;
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TQ1 = G::TQ1, WCM = G::WCM1, NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   __shared__ __attribute__((aligned(16))) T bs[2 * WCM];
   __shared__ T tl[2 * (NR + 1) * L];
@@ -291,20 +274,13 @@ __global__ void __launch_bounds__(256) bwt_inv1_kernel(const BwtArgs<T, L> a) {
 }
 
 // ---- generic per-axis passes: any even L <= MIFWT_MAX_FILT, any strides ------------------------------------------------------------------------
-struct AxisArgs {
-  const void* in0;  // analysis: x       synthesis: lo
-  const void* in1;  //                   synthesis: hi
-  void* out0;       // analysis: lo      synthesis: y
-  void* out1;       // analysis: hi
-  int64_t sig_s[3], lo_s[3], hi_s[3];  // (outer, axis, inner) strides in elements
-  int64_t outer, inner;
-  int n, m, src, filt_len, nt, nb, ntab;
+struct BwtAxisArgs : AxisArgsBase {
+  int src, nt, nb, ntab;
   const double* tab;
-  double lo[MIFWT_MAX_FILT], hi[MIFWT_MAX_FILT];
 };
 
 template <typename T, bool INVERSE>
-__global__ void __launch_bounds__(256) bwt_axis_generic(const AxisArgs a) {
+__global__ void __launch_bounds__(256) bwt_axis_generic(const BwtAxisArgs a) {
   const int L = a.filt_len, NT = a.nt, NB = a.nb, M = a.m;
   const int64_t len = INVERSE ? a.n : M;
   const int64_t total = a.outer * len * a.inner;
@@ -363,10 +339,7 @@ __global__ void __launch_bounds__(256) bwt_axis_generic(const AxisArgs a) {
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------------
 // 0 = not served by the fused kernels, MIFWT_ERR_BADARG = inconsistent, 1 = served
 int fused_check(const mifwt_level_desc* d, int inverse) {
-  if (!d) return MIFWT_ERR_BADARG;
-  if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0)
-    return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
+  if (const int bad = desc_prelude(d)) return bad;
   if (d->mode < MIFWT_MODE_ZERO || d->mode > MIFWT_MODE_SYMMETRIC) return MIFWT_ERR_BADARG;
   for (int ax = 0; ax < d->ndim; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];
@@ -374,68 +347,26 @@ int fused_check(const mifwt_level_desc* d, int inverse) {
     if (2 * m < d->filt_len) return MIFWT_ERR_BADARG;  // a level needs L <= N
   }
   (void)inverse;
-  if (d->ndim > 2 || d->filt_len > 20 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64)) return 0;
-  const int last = d->ndim;
-  if (d->sig_stride[last] != 1 || d->approx_stride[last] != 1 || d->detail_stride[last] != 1) return 0;
-  int64_t tiles = d->batch;
-  for (int ax = 0; ax < d->ndim; ++ax) {
+  for (int ax = 0; ax < d->ndim; ++ax)
     if (2 * d->coef_extent[ax] < 2 * (d->filt_len - 1)) return 0;  // the two ends overlap: no compact table
-    if (d->coef_extent[ax] > (1 << 29)) return 0;
-    tiles *= (d->coef_extent[ax] + 7) / 8;
-  }
-  if (tiles > INT32_MAX) return 0;
-  return 1;
+  return fused_envelope(d);
 }
 
 template <typename T, int L>
 int launch_fused(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* flo, const double* fhi,
                  const mifwt_bwt_tables* tb, hipStream_t stream) {
-  constexpr int E = BwtVec<T>::E;
   static_assert(FwdTile<T, L>::LDS2 <= 65536 && InvTile<T, L>::LDS2 <= 65536, "tile does not fit the default LDS allowance");
   BwtArgs<T, L> a;
-  const int nd = d->ndim, nb = 1 << nd;
-  for (int s = 0; s < 4; ++s) {
-    a.in[s] = nullptr;
-    a.out[s] = nullptr;
-  }
-  for (int s = 0; s < (inverse ? nb : 1); ++s) a.in[s] = in[s];
-  for (int s = 0; s < (inverse ? 1 : nb); ++s) a.out[s] = out[s];
-  a.sig_bs = d->sig_stride[0];
-  a.a_bs = d->approx_stride[0];
-  a.d_bs = d->detail_stride[0];
-  a.sig_rs = nd == 2 ? d->sig_stride[1] : 0;
-  a.a_rs = nd == 2 ? d->approx_stride[1] : 0;
-  a.d_rs = nd == 2 ? d->detail_stride[1] : 0;
+  fill_level_args(a, d, inverse, in, out, flo, fhi, Vec16<T>::E);
+  const int nd = d->ndim;
   a.batch = (int)d->batch;
-  a.n_r = nd == 2 ? (int)d->sig_extent[0] : 1;
-  a.m_r = nd == 2 ? (int)d->coef_extent[0] : 1;
-  a.n_c = (int)d->sig_extent[nd - 1];
-  a.m_c = (int)d->coef_extent[nd - 1];
   a.src_r = nd == 2 ? ext_index(a.n_r, a.n_r, d->mode) : -1;
   a.src_c = ext_index(a.n_c, a.n_c, d->mode);
-  const void* sig = inverse ? out[0] : in[0];
-  a.sig_vec = aligned16(sig) && a.sig_bs % E == 0 && a.sig_rs % E == 0;
-  a.coef_vec = a.a_bs % E == 0 && a.d_bs % E == 0 && a.a_rs % E == 0 && a.d_rs % E == 0;
-  for (int s = 0; s < nb; ++s) a.coef_vec = a.coef_vec && aligned16(inverse ? in[s] : (const void*)out[s]);
   a.tab = tb->rows;
-  for (int t = 0; t < L; ++t) {
-    a.lo[t] = (T)flo[t];
-    a.hi[t] = (T)fhi[t];
-  }
   if (d->batch == 0) return MIFWT_OK;
-  int64_t grid;
-  if (nd == 2) {
-    const int tcw = inverse ? InvTile<T, L>::TQC : FwdTile<T, L>::TC, trw = inverse ? InvTile<T, L>::TQ : FwdTile<T, L>::TR;
-    a.tiles_c = (a.m_c + tcw - 1) / tcw;
-    a.tiles_r = (a.m_r + trw - 1) / trw;
-    grid = (int64_t)a.tiles_c * a.tiles_r * d->batch;
-  } else {
-    const int tcw = inverse ? InvTile<T, L>::TQ1 : FwdTile<T, L>::TC1;
-    a.tiles_c = (a.m_c + tcw - 1) / tcw;
-    a.tiles_r = 1;
-    grid = (int64_t)a.tiles_c * d->batch;
-  }
-  if (grid > INT32_MAX) return MIFWT_ERR_UNSUPPORTED;
+  const int tcw = nd == 2 ? (inverse ? InvTile<T, L>::TQC : FwdTile<T, L>::TC) : (inverse ? InvTile<T, L>::TQ1 : FwdTile<T, L>::TC1);
+  const int64_t grid = cut_tiles(a, a.m_c, a.m_r, tcw, inverse ? InvTile<T, L>::TQ : FwdTile<T, L>::TR, d->batch);
+  if (grid < 0) return MIFWT_ERR_UNSUPPORTED;
   const dim3 g((unsigned)grid), blk(256);
   if (nd == 2) {
     if (inverse)
@@ -454,34 +385,18 @@ int launch_fused(const mifwt_level_desc* d, int inverse, const void* const* in, 
 template <typename T>
 int dispatch_len(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* flo, const double* fhi,
                  const mifwt_bwt_tables* tb, hipStream_t stream) {
-  switch (d->filt_len) {
-#define MIFWT_BWT_CASE(LEN) \
-  case LEN: return launch_fused<T, LEN>(d, inverse, in, out, flo, fhi, tb, stream);
-    MIFWT_BWT_CASE(2)
-    MIFWT_BWT_CASE(4)
-    MIFWT_BWT_CASE(6)
-    MIFWT_BWT_CASE(8)
-    MIFWT_BWT_CASE(10)
-    MIFWT_BWT_CASE(12)
-    MIFWT_BWT_CASE(14)
-    MIFWT_BWT_CASE(16)
-    MIFWT_BWT_CASE(18)
-    MIFWT_BWT_CASE(20)
-#undef MIFWT_BWT_CASE
-    default: return MIFWT_ERR_UNSUPPORTED;
-  }
+  return for_even_len(d->filt_len,
+                      [&](auto len) { return launch_fused<T, decltype(len)::value>(d, inverse, in, out, flo, fhi, tb, stream); });
 }
 
 int bwt_level(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
               const mifwt_bwt_tables* tb, void* stream) {
   const int ok = fused_check(d, inverse);
   if (ok < 0) return ok;
-  if (!lo || !hi || !tb || !tb->rows) return MIFWT_ERR_BADARG;
+  if (!tb || !tb->rows) return MIFWT_ERR_BADARG;
   const int L = d->filt_len;
   if (!table_fits(tb, L)) return MIFWT_ERR_BADARG;
-  for (int s = 0; s < (1 << (d->ndim > 2 ? 0 : d->ndim)); ++s)
-    if (!(inverse ? in[s] : (const void*)out[s])) return MIFWT_ERR_BADARG;
-  if (!(inverse ? (const void*)out[0] : in[0])) return MIFWT_ERR_BADARG;
+  if (const int bad = level_pointers(d, inverse, in, out, lo, hi)) return bad;
   if (!ok) return MIFWT_ERR_UNSUPPORTED;
   double flo[MIFWT_MAX_FILT], fhi[MIFWT_MAX_FILT];
   bank_taps(inverse, L, lo, hi, flo, fhi);
@@ -493,52 +408,25 @@ int bwt_level(const mifwt_level_desc* d, int inverse, const void* const* in, voi
 int bwt_axis(int inverse, int dtype, int filt_len, int mode, int64_t outer, int64_t n, int64_t inner, const void* in0, const void* in1,
              void* out0, void* out1, const int64_t* sig_s, const int64_t* lo_s, const int64_t* hi_s, const double* lo, const double* hi,
              const mifwt_bwt_tables* tb, void* stream) {
-  if (!in0 || !out0 || (inverse ? !in1 : !out1) || !sig_s || !lo_s || !hi_s || !lo || !hi || !tb || !tb->rows) return MIFWT_ERR_BADARG;
-  if (filt_len < 2 || (filt_len & 1) || filt_len > MIFWT_MAX_FILT || outer < 0 || inner < 0 || n < 1) return MIFWT_ERR_BADARG;
+  if (!tb || !tb->rows) return MIFWT_ERR_BADARG;
   if (mode < MIFWT_MODE_ZERO || mode > MIFWT_MODE_SYMMETRIC) return MIFWT_ERR_BADARG;
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return is_storage16(dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
+  if (const int bad = axis_check(inverse, dtype, filt_len, outer, n, inner, in0, in1, out0, out1, sig_s, lo_s, hi_s, lo, hi)) return bad;
   const int64_t m = (n + 1) / 2;
   if (2 * m < 2 * (int64_t)(filt_len - 1)) return filt_len <= 2 * m ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
   if (!table_fits(tb, filt_len)) return MIFWT_ERR_BADARG;
-  if (n > INT32_MAX / 4) return MIFWT_ERR_UNSUPPORTED;
-  AxisArgs a;
-  a.in0 = in0;
-  a.in1 = in1;
-  a.out0 = out0;
-  a.out1 = out1;
-  for (int i = 0; i < 3; ++i) {
-    a.sig_s[i] = sig_s[i];
-    a.lo_s[i] = lo_s[i];
-    a.hi_s[i] = hi_s[i];
-  }
-  a.outer = outer;
-  a.inner = inner;
-  a.n = (int)n;
-  a.m = (int)m;
+  double flo[MIFWT_MAX_FILT], fhi[MIFWT_MAX_FILT];
+  bank_taps(inverse, filt_len, lo, hi, flo, fhi);
+  BwtAxisArgs a;
+  if (const int bad = fill_axis_args(a, filt_len, outer, n, m, inner, in0, in1, out0, out1, sig_s, lo_s, hi_s, flo, fhi)) return bad;
   a.src = ext_index((int)n, (int)n, mode);
-  a.filt_len = filt_len;
   a.nt = tb->n_top;
   a.nb = tb->n_bot;
   a.ntab = a.nt + a.nb > 0 ? a.nt + a.nb : 1;
   a.tab = tb->rows;
-  bank_taps(inverse, filt_len, lo, hi, a.lo, a.hi);
   const int64_t total = outer * (inverse ? n : m) * inner;
   if (total == 0) return MIFWT_OK;
-  const int64_t blocks = (total + 255) / 256;
-  const dim3 g((unsigned)(blocks < 8192 ? blocks : 8192)), blk(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == MIFWT_F32) {
-    if (inverse)
-      hipLaunchKernelGGL((bwt_axis_generic<float, true>), g, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((bwt_axis_generic<float, false>), g, blk, 0, st, a);
-  } else {
-    if (inverse)
-      hipLaunchKernelGGL((bwt_axis_generic<double, true>), g, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((bwt_axis_generic<double, false>), g, blk, 0, st, a);
-  }
-  return hipGetLastError() == hipSuccess ? MIFWT_OK : MIFWT_ERR_LAUNCH;
+  return launch_axis(dtype, inverse, total, 8192, stream, a, bwt_axis_generic<float, false>, bwt_axis_generic<float, true>,
+                     bwt_axis_generic<double, false>, bwt_axis_generic<double, true>);
 }
 
 }  // namespace
@@ -553,30 +441,22 @@ int mifwt_bwt_supported(const mifwt_level_desc* desc, int direction) {
 }
 
 int mifwt_bwt_kernel_id(const mifwt_level_desc* desc, int direction) {
-  const int ok = mifwt_bwt_supported(desc, direction);
-  if (ok < 0) return ok;
-  return ok ? (direction ? MIFWT_KID_BWT_INV : MIFWT_KID_BWT_FWD) : MIFWT_ERR_UNSUPPORTED;
+  return mifwt::kernel_id_answer(mifwt_bwt_supported(desc, direction), direction, MIFWT_KID_BWT_FWD, MIFWT_KID_BWT_INV);
 }
 
 int mifwt_bwt_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* lo, const double* hi,
                   const mifwt_bwt_tables* tables, void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
   const void* in[4] = {x, nullptr, nullptr, nullptr};
-  void* out[4] = {approx, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) out[s] = details[s - 1];
+  void* out[4];
+  if (const int bad = mifwt::pack_bands<void*>(desc, approx, details, out)) return bad;
   return mifwt::bwt_level(desc, 0, in, out, lo, hi, tables, stream);
 }
 
 int mifwt_bwt_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* lo, const double* hi,
                   const mifwt_bwt_tables* tables, void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
-  const void* in[4] = {approx, nullptr, nullptr, nullptr};
+  const void* in[4];
   void* out[4] = {y, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) in[s] = details[s - 1];
+  if (const int bad = mifwt::pack_bands<const void*>(desc, approx, details, in)) return bad;
   return mifwt::bwt_level(desc, 1, in, out, lo, hi, tables, stream);
 }
 

@@ -34,7 +34,7 @@ namespace {
 // ---- brick geometry (compile time) -------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 struct Fwd3Tile {
-  static constexpr int E = BwtVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int TC = 8 * E;                             // coefficient columns per brick: 8 lanes x one 16-byte store
   static constexpr int TD = L <= 6 ? 4 : 3;                    // coefficient slices per brick
   static constexpr int TR = L <= 4 ? 8 : (L == 6 ? 6 : (E == 4 ? 4 : 3));  // coefficient rows per brick
@@ -49,7 +49,7 @@ struct Fwd3Tile {
 
 template <typename T, int L>
 struct Inv3Tile {
-  static constexpr int E = BwtVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int TQC = 8 * E;                            // coefficient columns per brick (2 TQC output samples)
   static constexpr int TQD = L <= 2 ? 4 : 2;                   // coefficient slices per brick
   static constexpr int TQR = L <= 2 ? 8 : (L == 8 && E == 2 ? 2 : 4);  // coefficient rows per brick
@@ -81,9 +81,9 @@ struct Bwt3Args {
 // apart in LDS, E columns at a time.  ws = first staged sample of the axis, pad = 2 * (first coefficient of the brick) - ws.
 template <typename T, int L>
 __device__ __forceinline__ void analysis_across3(const T* col, int pitch, bool edge, int ml, int m, int m_ext, int pad, int ws, const T* tl,
-                                                 const T (&flo)[L], const T (&fhi)[L], typename BwtVec<T>::type& lo,
-                                                 typename BwtVec<T>::type& hi) {
-  typedef typename BwtVec<T>::type V;
+                                                 const T (&flo)[L], const T (&fhi)[L], typename Vec16<T>::type& lo,
+                                                 typename Vec16<T>::type& hi) {
+  typedef typename Vec16<T>::type V;
   constexpr int NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   V sl = V(0), sh = V(0);
   if (!edge || (m >= NT && m < m_ext - NB)) {
@@ -122,7 +122,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char bwt3_lds[];
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
   typedef Fwd3Tile<T, L> G;
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC, TR = G::TR, TD = G::TD, WC = G::WC, WR = G::WR, WD = G::WD, CG = TC / E;
   constexpr int NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   static_assert(WC >= 2 * TC, "the width image of a row must fit into the row it replaces");
@@ -240,7 +240,7 @@ __global__ void __launch_bounds__(256) bwt_fwd3_kernel(const Bwt3Args<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) bwt_inv3_kernel(const Bwt3Args<T, L> a) {
   typedef Inv3Tile<T, L> G;
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TQC = G::TQC, TQR = G::TQR, TQD = G::TQD, WCM = G::WCM, WRM = G::WRM, WDM = G::WDM, CV = WCM / E;
   constexpr int NR = Rows<L>::NR;
   T* const bs = reinterpret_cast<T*>(bwt3_lds);  // [8][WDM][WRM][WCM], then the images of the depth and the height pass
@@ -372,7 +372,7 @@ int fused3_check(const mifwt_level_desc* d) {
 template <typename T, int L>
 int launch_fused3(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* flo, const double* fhi,
                   const mifwt_bwt_tables* tb, hipStream_t stream) {
-  constexpr int E = BwtVec<T>::E;
+  constexpr int E = Vec16<T>::E;
   typedef Fwd3Tile<T, L> GF;
   typedef Inv3Tile<T, L> GI;
   static_assert(GF::LDS3 <= 80 * 1024, "analysis brick: two workgroups per CU");

@@ -10,27 +10,14 @@
 //   p = (L/2 - n) & 1,  m0 = (n + p - L/2) / 2.
 // Analysis applies the rows of a bank, synthesis the transposed bank; the adjoint of either is the other kernel with the same bank.
 // An odd signal extent has one virtual sample at its end (index map, `mode`); synthesis simply does not store it.
+// The 16-byte vectors, the stores and the row pass of an interior window come from mifwt_level_tile.h, which the fused levels of the
+// other modes share; only what is about the row bank is here.
 #pragma once
-#include "mifwt_common.h"
+#include "mifwt_level_tile.h"
 
 namespace mifwt {
 
 namespace {
-
-template <typename T>
-struct BwtVec;
-template <>
-struct BwtVec<float> {
-  static constexpr int E = 4;
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <>
-struct BwtVec<double> {
-  static constexpr int E = 2;
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-
-constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 template <int L>
 struct Rows {
@@ -58,7 +45,7 @@ __device__ __forceinline__ void load_table(T* tl, const Args& a) {
 // virtual sample: row[src].  `row` == nullptr: zeros.
 template <typename T, int E>
 __device__ __forceinline__ void stage_vec(T* dst, const T* __restrict__ row, int g0, int n, int n_pad, int src, bool vec_ok) {
-  typedef typename BwtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   V v;
   if (row && vec_ok && g0 >= 0 && g0 + E <= n) {
     v = *reinterpret_cast<const V*>(row + g0);
@@ -82,31 +69,12 @@ __device__ __forceinline__ void stage_vec(T* dst, const T* __restrict__ row, int
 // E consecutive analysis outputs (both bands) from a staged row.  xr: LDS row, `pad` = staged samples left of sample 2 * m_first_of_tile.
 template <typename T, int L, bool EDGE>
 __device__ __forceinline__ void analysis_run(const T* xr, int pad, int ml, int m_glob, int m_ext, const T* tl, const T (&flo)[L],
-                                             const T (&fhi)[L], typename BwtVec<T>::type& lo, typename BwtVec<T>::type& hi) {
-  constexpr int E = BwtVec<T>::E, NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
+                                             const T (&fhi)[L], typename Vec16<T>::type& lo, typename Vec16<T>::type& hi) {
+  constexpr int E = Vec16<T>::E, NT = Rows<L>::NT, NB = Rows<L>::NB, NR = NT + NB;
   if (!EDGE) {
-    // the window starts OFF samples into a 16-byte aligned run of the staged row (2 ml, pad and PADI are multiples of E)
-    typedef typename BwtVec<T>::type V;
-    constexpr int PADI = round_up(L / 2 - 1, E), OFF = PADI - (L / 2 - 1), NV = (OFF + 2 * E + L - 2 + E - 1) / E;
-    T w[NV * E];
-    const T* p = xr + 2 * ml + pad - PADI;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const V v = *reinterpret_cast<const V*>(p + i * E);
-#pragma unroll
-      for (int e = 0; e < E; ++e) w[i * E + e] = v[e];
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      T sl = T(0), sh = T(0);
-#pragma unroll
-      for (int k = 0; k < L; ++k) {
-        sl = fma(flo[L - 1 - k], w[OFF + 2 * e + k], sl);
-        sh = fma(fhi[L - 1 - k], w[OFF + 2 * e + k], sh);
-      }
-      lo[e] = sl;
-      hi[e] = sh;
-    }
+    // the window starts OFF samples into a 16-byte aligned run of the staged row (2 ml, pad and the window's PAD are multiples of E)
+    typedef RowWindow<T, L, L / 2 - 1> W;
+    window_run<T, L, L / 2 - 1>(xr + 2 * ml + pad - W::PAD, flo, fhi, lo, hi);
   } else {
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -133,18 +101,6 @@ __device__ __forceinline__ void analysis_run(const T* xr, int pad, int ml, int m
       lo[e] = sl;
       hi[e] = sh;
     }
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void store_vec(T* p, const typename BwtVec<T>::type& v, int valid, bool vec_ok) {
-  constexpr int E = BwtVec<T>::E;
-  if (vec_ok && valid >= E) {
-    *reinterpret_cast<typename BwtVec<T>::type*>(p) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-      if (e < valid) p[e] = v[e];
   }
 }
 
@@ -195,8 +151,6 @@ __device__ __forceinline__ V synthesis_point(int n, int m_org, int m_ext, const 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // the table of a bank of L taps has ceil((L-2)/4) top and floor(L/4) bottom rows
 bool table_fits(const mifwt_bwt_tables* tb, int L) { return tb->n_top == (L - 2 + 3) / 4 && tb->n_bot == L / 4; }
 

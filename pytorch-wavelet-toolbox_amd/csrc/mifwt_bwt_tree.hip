@@ -43,8 +43,8 @@ extern __shared__ __attribute__((aligned(16))) unsigned char bwt_tree_lds[];
 
 template <typename T>
 __device__ __forceinline__ void tree_stage(T* img, const T* __restrict__ src, int n, bool vec) {
-  typedef typename BwtVec<T>::type V;
-  constexpr int E = BwtVec<T>::E;
+  typedef typename Vec16<T>::type V;
+  constexpr int E = Vec16<T>::E;
   if (vec) {
     for (int i = threadIdx.x; i < n / E; i += blockDim.x) reinterpret_cast<V*>(img)[i] = reinterpret_cast<const V*>(src)[i];
   } else {
@@ -54,8 +54,8 @@ __device__ __forceinline__ void tree_stage(T* img, const T* __restrict__ src, in
 
 template <typename T>
 __device__ __forceinline__ void tree_flush(T* __restrict__ dst, const T* img, int n, bool vec) {
-  typedef typename BwtVec<T>::type V;
-  constexpr int E = BwtVec<T>::E;
+  typedef typename Vec16<T>::type V;
+  constexpr int E = Vec16<T>::E;
   if (vec) {
     for (int i = threadIdx.x; i < n / E; i += blockDim.x) reinterpret_cast<V*>(dst)[i] = reinterpret_cast<const V*>(img)[i];
   } else {
@@ -192,7 +192,7 @@ int tree_levels(int dtype, int filt_len, int64_t n, int max_levels) {
 template <typename T, int L>
 int tree_launch(int inverse, int64_t rows, int n, int64_t in_rs, int nlevels, const void* in, void* const* levels, const double* flo,
                 const double* fhi, const mifwt_bwt_tables* tb, hipStream_t stream) {
-  constexpr int E = BwtVec<T>::E;
+  constexpr int E = Vec16<T>::E;
   TreeArgs<T, L> a;
   a.in = static_cast<const T*>(in);
   a.in_rs = in_rs;
@@ -229,22 +229,9 @@ int tree_launch(int inverse, int64_t rows, int n, int64_t in_rs, int nlevels, co
 template <typename T>
 int tree_dispatch(int filt_len, int inverse, int64_t rows, int n, int64_t in_rs, int nlevels, const void* in, void* const* levels,
                   const double* flo, const double* fhi, const mifwt_bwt_tables* tb, hipStream_t stream) {
-  switch (filt_len) {
-#define MIFWT_TREE_CASE(LEN) \
-  case LEN: return tree_launch<T, LEN>(inverse, rows, n, in_rs, nlevels, in, levels, flo, fhi, tb, stream);
-    MIFWT_TREE_CASE(2)
-    MIFWT_TREE_CASE(4)
-    MIFWT_TREE_CASE(6)
-    MIFWT_TREE_CASE(8)
-    MIFWT_TREE_CASE(10)
-    MIFWT_TREE_CASE(12)
-    MIFWT_TREE_CASE(14)
-    MIFWT_TREE_CASE(16)
-    MIFWT_TREE_CASE(18)
-    MIFWT_TREE_CASE(20)
-#undef MIFWT_TREE_CASE
-    default: return MIFWT_ERR_UNSUPPORTED;
-  }
+  return for_even_len(filt_len, [&](auto len) {
+    return tree_launch<T, decltype(len)::value>(inverse, rows, n, in_rs, nlevels, in, levels, flo, fhi, tb, stream);
+  });
 }
 
 int tree_call(int inverse, int dtype, int filt_len, int64_t rows, int64_t n, int64_t in_rs, int nlevels, const void* in,

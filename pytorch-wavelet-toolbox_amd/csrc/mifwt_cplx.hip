@@ -25,7 +25,10 @@
 //        along the rows from LDS, 16 bytes of components per lane.  1-D: one pair of samples per thread.
 // Both components run the same instructions in the same order (component-wise fma chains), no atomics: the real plane of every output is
 // a function of the real plane of the input alone, bit for bit.  Batch, plane and row offsets are int64.
-#include "mifwt_common.h"
+// Shared with the other fused-level units, from mifwt_level_tile.h: the common kernel arguments and their fill (with EC for the elements
+// per 16 bytes, strides in complex elements), the tile cut, the descriptor prelude and envelope, the length dispatch and the packing of
+// the level entries.  Every kernel body is this unit's own: its row pass is channel-aware and its window has an odd pitch.
+#include "mifwt_level_tile.h"
 
 namespace mifwt {
 
@@ -88,18 +91,11 @@ struct CInvGeo {
   static constexpr int LDS2 = 2 * KR * TSC * 2 * (int)sizeof(T);
 };
 
+// Strides and extents in COMPLEX elements; synthesis: n_r / n_c are the cropped output extents.  dec_lo / dec_hi (analysis), rec_lo /
+// rec_hi (synthesis)
 template <typename T, int L>
-struct CplxArgs {
-  const void* in[4];  // analysis: in[0] = x;  synthesis: the 2^ndim bands
-  void* out[4];       // analysis: the bands;  synthesis: out[0] = y
-  int64_t sig_bs, sig_rs;          // signal side: batch / row stride in COMPLEX elements (samples contiguous).  1-D: rows = batch
-  int64_t a_bs, a_rs, d_bs, d_rs;  // band 0 / bands 1..: batch / row strides
-  int n_r, n_c;                    // signal extents (1-D: n_r = 1); synthesis: the cropped output extents
-  int m_r, m_c;                    // coefficient extents
-  int sig_vec, coef_vec;           // 16-byte accesses allowed on the signal / coefficient side
-  int tiles_c, tiles_r;
-  int mode;                        // enum mifwt_mode (analysis)
-  T lo[L], hi[L];                  // dec_lo / dec_hi (analysis), rec_lo / rec_hi (synthesis), PyWavelets order
+struct CplxArgs : LevelArgs<T, L> {
+  int mode;  // enum mifwt_mode (analysis)
 };
 
 // EC complex elements from `valid` on: one 16-byte store, or element stores
@@ -377,14 +373,11 @@ __global__ void __launch_bounds__(256) cplx_inv1_kernel(const CplxArgs<T, L> a) 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
-bool cplx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // 0 = not served by the fused kernels, MIFWT_ERR_BADARG = inconsistent, MIFWT_ERR_UNSUPPORTED = a component type without kernels, 1 = served
 int cplx_check(const mifwt_level_desc* d, int direction) {
-  if (!d || (direction != 0 && direction != 1)) return MIFWT_ERR_BADARG;
-  if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0)
-    return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64) return is_storage16(d->dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
+  if (const int bad = desc_prelude(d)) return bad;
+  if (direction != 0 && direction != 1) return MIFWT_ERR_BADARG;
+  if (is_storage16(d->dtype)) return MIFWT_ERR_UNSUPPORTED;
   if (direction == 0 && (d->mode < MIFWT_MODE_ZERO || d->mode > MIFWT_MODE_SYMMETRIC)) return MIFWT_ERR_BADARG;
   for (int ax = 0; ax < d->ndim; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];
@@ -395,64 +388,24 @@ int cplx_check(const mifwt_level_desc* d, int direction) {
       if (m < 1 || n < 1 || (n != full && n != full - 1)) return MIFWT_ERR_BADARG;
     }
   }
-  if (d->ndim > 2 || d->filt_len > 20) return 0;
-  const int last = d->ndim;
-  if (d->sig_stride[last] != 1 || d->approx_stride[last] != 1 || d->detail_stride[last] != 1) return 0;
-  int64_t tiles = d->batch;
-  for (int ax = 0; ax < d->ndim; ++ax) {
-    if (d->coef_extent[ax] > (1 << 29)) return 0;
-    tiles *= (d->coef_extent[ax] + 7) / 8;  // (more tiles than either direction cuts)
-  }
-  if (tiles > INT32_MAX) return 0;
-  return 1;
+  return fused_envelope(d);
 }
 
 template <typename T, int L>
 int cplx_launch(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
                 hipStream_t stream) {
-  constexpr int EC = Cplx<T>::EC;
   typedef CFwdGeo<T, L> FG;
   typedef CInvGeo<T, L> IG;
   static_assert(FG::LDS2 <= 65536 && IG::LDS2 <= 65536, "tile does not fit the default LDS allowance");
   CplxArgs<T, L> a;
-  const int nd = d->ndim, nb = 1 << nd;
-  for (int s = 0; s < 4; ++s) {
-    a.in[s] = nullptr;
-    a.out[s] = nullptr;
-  }
-  for (int s = 0; s < (inverse ? nb : 1); ++s) a.in[s] = in[s];
-  for (int s = 0; s < (inverse ? 1 : nb); ++s) a.out[s] = out[s];
-  a.sig_bs = d->sig_stride[0];
-  a.a_bs = d->approx_stride[0];
-  a.d_bs = d->detail_stride[0];
-  a.sig_rs = nd == 2 ? d->sig_stride[1] : 0;
-  a.a_rs = nd == 2 ? d->approx_stride[1] : 0;
-  a.d_rs = nd == 2 ? d->detail_stride[1] : 0;
-  a.n_r = nd == 2 ? (int)d->sig_extent[0] : 1;
-  a.m_r = nd == 2 ? (int)d->coef_extent[0] : 1;
-  a.n_c = (int)d->sig_extent[nd - 1];
-  a.m_c = (int)d->coef_extent[nd - 1];
+  fill_level_args(a, d, inverse, in, out, lo, hi, Cplx<T>::EC);
   a.mode = d->mode;
-  const void* sig = inverse ? out[0] : in[0];
-  a.sig_vec = cplx_aligned16(sig) && a.sig_bs % EC == 0 && a.sig_rs % EC == 0;
-  a.coef_vec = a.a_bs % EC == 0 && a.d_bs % EC == 0 && a.a_rs % EC == 0 && a.d_rs % EC == 0;
-  for (int s = 0; s < nb; ++s) a.coef_vec = a.coef_vec && cplx_aligned16(inverse ? in[s] : (const void*)out[s]);
-  for (int t = 0; t < L; ++t) {
-    a.lo[t] = (T)lo[t];
-    a.hi[t] = (T)hi[t];
-  }
   if (d->batch == 0) return MIFWT_OK;
-  int64_t grid;
-  if (nd == 2) {
-    a.tiles_c = inverse ? (a.n_c + IG::TSC - 1) / IG::TSC : (a.m_c + FG::TC - 1) / FG::TC;
-    a.tiles_r = inverse ? (a.n_r + IG::TSR - 1) / IG::TSR : (a.m_r + FG::TR - 1) / FG::TR;
-    grid = (int64_t)a.tiles_c * a.tiles_r * d->batch;
-  } else {
-    a.tiles_c = inverse ? (a.n_c + IG::TS1 - 1) / IG::TS1 : (a.m_c + FG::TC1 - 1) / FG::TC1;
-    a.tiles_r = 1;
-    grid = (int64_t)a.tiles_c * d->batch;
-  }
-  if (grid > INT32_MAX) return MIFWT_ERR_UNSUPPORTED;
+  const int nd = d->ndim;
+  // analysis cuts the coefficients, synthesis the samples
+  const int tcw = nd == 2 ? (inverse ? IG::TSC : FG::TC) : (inverse ? IG::TS1 : FG::TC1);
+  const int64_t grid = inverse ? cut_tiles(a, a.n_c, a.n_r, tcw, IG::TSR, d->batch) : cut_tiles(a, a.m_c, a.m_r, tcw, FG::TR, d->batch);
+  if (grid < 0) return MIFWT_ERR_UNSUPPORTED;
   const dim3 g((unsigned)grid), blk(256);
   if (nd == 2) {
     if (inverse)
@@ -473,32 +426,14 @@ int cplx_launch(const mifwt_level_desc* d, int inverse, const void* const* in, v
 template <typename T>
 int cplx_dispatch_len(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
                       hipStream_t stream) {
-  switch (d->filt_len) {
-#define MIFWT_CPLX_CASE(LEN) \
-  case LEN: return cplx_launch<T, LEN>(d, inverse, in, out, lo, hi, stream);
-    MIFWT_CPLX_CASE(2)
-    MIFWT_CPLX_CASE(4)
-    MIFWT_CPLX_CASE(6)
-    MIFWT_CPLX_CASE(8)
-    MIFWT_CPLX_CASE(10)
-    MIFWT_CPLX_CASE(12)
-    MIFWT_CPLX_CASE(14)
-    MIFWT_CPLX_CASE(16)
-    MIFWT_CPLX_CASE(18)
-    MIFWT_CPLX_CASE(20)
-#undef MIFWT_CPLX_CASE
-    default: return MIFWT_ERR_UNSUPPORTED;
-  }
+  return for_even_len(d->filt_len, [&](auto len) { return cplx_launch<T, decltype(len)::value>(d, inverse, in, out, lo, hi, stream); });
 }
 
 int cplx_level(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
                void* stream) {
   const int ok = cplx_check(d, inverse);
   if (ok < 0) return ok;
-  if (!lo || !hi) return MIFWT_ERR_BADARG;
-  for (int s = 0; s < (1 << (d->ndim > 2 ? 0 : d->ndim)); ++s)
-    if (!(inverse ? in[s] : (const void*)out[s])) return MIFWT_ERR_BADARG;
-  if (!(inverse ? (const void*)out[0] : in[0])) return MIFWT_ERR_BADARG;
+  if (const int bad = level_pointers(d, inverse, in, out, lo, hi)) return bad;
   if (!ok) return MIFWT_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return d->dtype == MIFWT_F32 ? cplx_dispatch_len<float>(d, inverse, in, out, lo, hi, st)
@@ -514,30 +449,22 @@ extern "C" {
 int mifwt_cplx_supported(const mifwt_level_desc* desc, int direction) { return mifwt::cplx_check(desc, direction); }
 
 int mifwt_cplx_kernel_id(const mifwt_level_desc* desc, int direction) {
-  const int ok = mifwt_cplx_supported(desc, direction);
-  if (ok < 0) return ok;
-  return ok ? (direction ? MIFWT_KID_CPLX_INV : MIFWT_KID_CPLX_FWD) : MIFWT_ERR_UNSUPPORTED;
+  return mifwt::kernel_id_answer(mifwt_cplx_supported(desc, direction), direction, MIFWT_KID_CPLX_FWD, MIFWT_KID_CPLX_INV);
 }
 
 int mifwt_cplx_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* dec_lo,
                    const double* dec_hi, void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
   const void* in[4] = {x, nullptr, nullptr, nullptr};
-  void* out[4] = {approx, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) out[s] = details[s - 1];
+  void* out[4];
+  if (const int bad = mifwt::pack_bands<void*>(desc, approx, details, out)) return bad;
   return mifwt::cplx_level(desc, 0, in, out, dec_lo, dec_hi, stream);
 }
 
 int mifwt_cplx_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* rec_lo,
                    const double* rec_hi, void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
-  const void* in[4] = {approx, nullptr, nullptr, nullptr};
+  const void* in[4];
   void* out[4] = {y, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) in[s] = details[s - 1];
+  if (const int bad = mifwt::pack_bands<const void*>(desc, approx, details, in)) return bad;
   return mifwt::cplx_level(desc, 1, in, out, rec_lo, rec_hi, stream);
 }
 

@@ -20,26 +20,15 @@
 //   (global -> LDS, two planes: low / high band along the rows), then the row adjoint from LDS, and stores 16 bytes per lane.
 // Everything else (L > 20, any strides, the depth axis of a 3-D level) runs ext_axis_kernel: one thread per output, run-time tap loop,
 // double accumulators.
-#include "mifwt_common.h"
+// Shared with the other fused-level units, from mifwt_level_tile.h: the 16-byte vectors, the row pass over the aligned window (left
+// reach H = L - 2), the tap step of the column pass and the band stores, the common kernel arguments and their fill, the tile cut, the
+// descriptor prelude and envelope, the length dispatch, the packing of the level entries and the axis-pass arguments and launcher.
+// Here: the value map, the staging with its partial windows, the geometry, the adjoint kernels and the launches.
+#include "mifwt_level_tile.h"
 
 namespace mifwt {
 
 namespace {
-
-template <typename T>
-struct ExtVec;
-template <>
-struct ExtVec<float> {
-  static constexpr int E = 4;
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <>
-struct ExtVec<double> {
-  static constexpr int E = 2;
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-
-constexpr int rup(int v, int m) { return (v + m - 1) / m * m; }
 
 // ---- the extension: xe[i] = w[0] x[idx[0]] + w[1] x[idx[1]] + w[2] x[idx[2]] (a weight 0 marks an unused term) -----------------------------
 struct Terms {
@@ -158,25 +147,23 @@ __device__ __forceinline__ void adjoint_at(int s, int n, int m, int L, int mode,
 // ---- tile geometry (compile time; static LDS below 64 KB, at least two workgroups per CU) ----------------------------------------------
 template <typename T, int L>
 struct FwdGeo {
-  static constexpr int E = ExtVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int H = L - 2;                     // samples of the window left of sample 2 k
   static constexpr int TC = 16 * E;                   // coefficient columns per tile: 16 lanes x one 16-byte store
   static constexpr int TR = 16;                       // coefficient rows per tile: one column-pass item per thread
-  static constexpr int PAD = rup(H, E);               // staged columns left of sample 2 mc0 (keeps the staged vectors aligned)
-  static constexpr int OFF = PAD - H;                 // window of output 0 starts at staged column OFF
-  static constexpr int NV = (OFF + 2 * E + L - 2 + E - 1) / E;  // 16-byte pieces of the window of E outputs
-  static constexpr int WC = rup(PAD + 2 * TC, E);
+  static constexpr int PAD = RowWindow<T, L, H>::PAD;  // staged columns left of sample 2 mc0 (keeps the staged vectors aligned)
+  static constexpr int WC = round_up(PAD + 2 * TC, E);
   static constexpr int XP = WC + E;                   // pitch of the staged window (a lane's last piece may end inside the pad)
   static constexpr int WR = 2 * TR + L - 2;
   static constexpr int HP = TC + E;                   // pitch of the row-filtered planes: one access width against bank conflicts
   static constexpr int TC1 = 256 * E;                 // 1-D: coefficients per workgroup
-  static constexpr int WC1 = rup(PAD + 2 * TC1, E);
+  static constexpr int WC1 = round_up(PAD + 2 * TC1, E);
   static constexpr int LDS2 = (WR * XP + 2 * WR * HP) * (int)sizeof(T);
 };
 
 template <typename T, int L>
 struct AdjGeo {
-  static constexpr int E = ExtVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int TSC = 16 * E;                  // sample columns per tile
   static constexpr int TSR = 16;                      // sample rows per tile
   static constexpr int KWR = TSR / 2 + 3 * L / 2;     // coefficient rows behind a tile's rows: both pads where the axis is short
@@ -184,38 +171,18 @@ struct AdjGeo {
   static constexpr int LDS2 = 2 * KWR * TSC * (int)sizeof(T);
 };
 
+// analysis and adjoint take dec_lo / dec_hi;  coefficient extents = floor((n + L - 1) / 2)
 template <typename T, int L>
-struct ExtArgs {
-  const void* in[4];  // analysis: in[0] = x;  adjoint: the 2^ndim band gradients
-  void* out[4];       // analysis: the bands;  adjoint: out[0] = g_x
-  int64_t sig_bs, sig_rs;          // signal side: batch / row stride (elements; samples contiguous).  1-D: rows = batch
-  int64_t a_bs, a_rs, d_bs, d_rs;  // band 0 / bands 1..: batch / row strides
-  int n_r, n_c;                    // signal extents (1-D: n_r = 1)
-  int m_r, m_c;                    // coefficient extents = floor((n + L - 1) / 2)
-  int sig_vec, coef_vec;           // 16-byte accesses allowed on the signal / coefficient side
-  int tiles_c, tiles_r;
-  int mode;                        // MIFWT_EXT_*
-  T lo[L], hi[L];                  // dec_lo / dec_hi, PyWavelets order
+struct ExtArgs : LevelArgs<T, L> {
+  int mode;  // MIFWT_EXT_*
 };
-
-template <typename T>
-__device__ __forceinline__ void store_vec(T* p, const typename ExtVec<T>::type& v, int valid, bool vec_ok) {
-  constexpr int E = ExtVec<T>::E;
-  if (vec_ok && valid >= E) {
-    *reinterpret_cast<typename ExtVec<T>::type*>(p) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-      if (e < valid) p[e] = v[e];
-  }
-}
 
 // E staged samples of extended row `gr` from extended column g0 (a multiple of E).  `mapped` = the tile's window leaves the plane.
 template <typename T>
 __device__ __forceinline__ void stage_ext(T* dst, const T* __restrict__ plane, int64_t rs, int gr, int g0, int n_r, int n_c, int mode,
                                           bool vec_ok, bool mapped) {
-  constexpr int E = ExtVec<T>::E;
-  typedef typename ExtVec<T>::type V;
+  constexpr int E = Vec16<T>::E;
+  typedef typename Vec16<T>::type V;
   const bool row_in = !mapped || (gr >= 0 && gr < n_r);
   const bool col_in = !mapped || (g0 >= 0 && g0 + E <= n_c);
   if (row_in && col_in) {
@@ -241,38 +208,11 @@ __device__ __forceinline__ void stage_ext(T* dst, const T* __restrict__ plane, i
   }
 }
 
-// E consecutive outputs of both filters from a staged row; `p` = 16-byte aligned LDS address of staged column 2 * (first output)
-template <typename T, int L>
-__device__ __forceinline__ void analysis_run(const T* p, const T (&flo)[L], const T (&fhi)[L], typename ExtVec<T>::type& lo,
-                                             typename ExtVec<T>::type& hi) {
-  typedef FwdGeo<T, L> G;
-  typedef typename ExtVec<T>::type V;
-  constexpr int E = G::E, OFF = G::OFF, NV = G::NV;
-  T w[NV * E];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const V v = *reinterpret_cast<const V*>(p + i * E);
-#pragma unroll
-    for (int e = 0; e < E; ++e) w[i * E + e] = v[e];
-  }
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    T sl = T(0), sh = T(0);
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-      sl = fma(flo[L - 1 - k], w[OFF + 2 * e + k], sl);
-      sh = fma(fhi[L - 1 - k], w[OFF + 2 * e + k], sh);
-    }
-    lo[e] = sl;
-    hi[e] = sh;
-  }
-}
-
 // ---- analysis, 2-D ---------------------------------------------------------------------------------------------------------------------
 template <typename T, int L>
 __global__ void __launch_bounds__(256) ext_fwd2_kernel(const ExtArgs<T, L> a) {
   typedef FwdGeo<T, L> G;
-  typedef typename ExtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC, TR = G::TR, H = G::H, WC = G::WC, WR = G::WR, XP = G::XP, HP = G::HP;
   __shared__ __attribute__((aligned(16))) T xs[WR * XP];
   __shared__ __attribute__((aligned(16))) T hs[2 * WR * HP];
@@ -304,7 +244,7 @@ __global__ void __launch_bounds__(256) ext_fwd2_kernel(const ExtArgs<T, L> a) {
   for (int i = tid; i < wr * tcg; i += 256) {
     const int r = i / tcg, cg = i - r * tcg;
     V lo, hi;
-    analysis_run<T, L>(xs + r * XP + 2 * cg * E, a.lo, a.hi, lo, hi);
+    window_run<T, L, H>(xs + r * XP + 2 * cg * E, a.lo, a.hi, lo, hi);
     *reinterpret_cast<V*>(hs + r * HP + cg * E) = lo;
     *reinterpret_cast<V*>(hs + (WR + r) * HP + cg * E) = hi;
   }
@@ -318,22 +258,8 @@ __global__ void __launch_bounds__(256) ext_fwd2_kernel(const ExtArgs<T, L> a) {
     const T* hl0 = hs + (2 * ro) * HP + cg * E;
     const T* hh0 = hl0 + WR * HP;
 #pragma unroll
-    for (int k = 0; k < L; ++k) {
-      const V vl = *reinterpret_cast<const V*>(hl0 + k * HP);
-      const V vh = *reinterpret_cast<const V*>(hh0 + k * HP);
-      const T cl = a.lo[L - 1 - k], ch = a.hi[L - 1 - k];
-      ll += cl * vl;
-      lh += cl * vh;
-      hl += ch * vl;
-      hh += ch * vh;
-    }
-    const int valid = a.m_c - mc;
-    const int64_t oa = (int64_t)b * a.a_bs + (int64_t)m * a.a_rs + mc;
-    const int64_t od = (int64_t)b * a.d_bs + (int64_t)m * a.d_rs + mc;
-    store_vec<T>(static_cast<T*>(a.out[0]) + oa, ll, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[1]) + od, lh, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[2]) + od, hl, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[3]) + od, hh, valid, a.coef_vec);
+    for (int k = 0; k < L; ++k) column_tap<T>(hl0 + k * HP, hh0 + k * HP, a.lo[L - 1 - k], a.hi[L - 1 - k], ll, lh, hl, hh);
+    store_bands<T, L>(a, b, m, mc, ll, lh, hl, hh);
   }
 }
 
@@ -341,7 +267,7 @@ __global__ void __launch_bounds__(256) ext_fwd2_kernel(const ExtArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) ext_fwd1_kernel(const ExtArgs<T, L> a) {
   typedef FwdGeo<T, L> G;
-  typedef typename ExtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC1, WC = G::WC1;
   __shared__ __attribute__((aligned(16))) T xs[WC + E];
   const int tid = threadIdx.x;
@@ -361,7 +287,7 @@ __global__ void __launch_bounds__(256) ext_fwd1_kernel(const ExtArgs<T, L> a) {
   const int mc = mc0 + tid * E;
   if (mc >= a.m_c) return;
   V lo, hi;
-  analysis_run<T, L>(xs + 2 * tid * E, a.lo, a.hi, lo, hi);
+  window_run<T, L, G::H>(xs + 2 * tid * E, a.lo, a.hi, lo, hi);
   store_vec<T>(static_cast<T*>(a.out[0]) + (int64_t)b * a.a_bs + mc, lo, a.m_c - mc, a.coef_vec);
   store_vec<T>(static_cast<T*>(a.out[1]) + (int64_t)b * a.d_bs + mc, hi, a.m_c - mc, a.coef_vec);
 }
@@ -370,7 +296,7 @@ __global__ void __launch_bounds__(256) ext_fwd1_kernel(const ExtArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) ext_adj2_kernel(const ExtArgs<T, L> a) {
   typedef AdjGeo<T, L> G;
-  typedef typename ExtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TSC = G::TSC, TSR = G::TSR, KWR = G::KWR;
   __shared__ __attribute__((aligned(16))) T us[2 * KWR * TSC];  // [band along the rows][coefficient row - k_lo][sample column]
   const int tid = threadIdx.x;
@@ -427,7 +353,7 @@ __global__ void __launch_bounds__(256) ext_adj2_kernel(const ExtArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) ext_adj1_kernel(const ExtArgs<T, L> a) {
   typedef AdjGeo<T, L> G;
-  typedef typename ExtVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TS1 = G::TS1;
   const int tc = blockIdx.x % a.tiles_c;
   const int b = blockIdx.x / a.tiles_c;
@@ -448,19 +374,12 @@ __global__ void __launch_bounds__(256) ext_adj1_kernel(const ExtArgs<T, L> a) {
 }
 
 // ---- one axis of [outer, n, inner] arrays: any even L <= MIFWT_MAX_FILT, any strides -----------------------------------------------------------
-struct AxisArgs {
-  const void* in0;  // analysis: x       adjoint: g_lo
-  const void* in1;  //                   adjoint: g_hi
-  void* out0;       // analysis: lo      adjoint: g_x
-  void* out1;       // analysis: hi
-  int64_t sig_s[3], lo_s[3], hi_s[3];  // (outer, axis, inner) strides in elements
-  int64_t outer, inner;
-  int n, m, filt_len, mode;
-  double lo[MIFWT_MAX_FILT], hi[MIFWT_MAX_FILT];
+struct ExtAxisArgs : AxisArgsBase {
+  int mode;  // MIFWT_EXT_*
 };
 
 template <typename T, bool ADJOINT>
-__global__ void __launch_bounds__(256) ext_axis_kernel(const AxisArgs a) {
+__global__ void __launch_bounds__(256) ext_axis_kernel(const ExtAxisArgs a) {
   const int L = a.filt_len;
   const int64_t len = ADJOINT ? a.n : a.m;
   const int64_t total = a.outer * len * a.inner;
@@ -493,78 +412,36 @@ __global__ void __launch_bounds__(256) ext_axis_kernel(const AxisArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 bool mode_ok(int ext_mode) {
   return ext_mode == MIFWT_EXT_SMOOTH || ext_mode == MIFWT_EXT_ANTISYMMETRIC || ext_mode == MIFWT_EXT_ANTIREFLECT;
 }
 
 // 0 = not served by the fused kernels, MIFWT_ERR_BADARG = inconsistent, 1 = served
 int fused_check(const mifwt_level_desc* d, int ext_mode) {
-  if (!d || !mode_ok(ext_mode)) return MIFWT_ERR_BADARG;
-  if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0)
-    return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
+  if (const int bad = desc_prelude(d)) return bad;
+  if (!mode_ok(ext_mode)) return MIFWT_ERR_BADARG;
   for (int ax = 0; ax < d->ndim; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];
     if (n < 1 || m != (n + d->filt_len - 1) / 2) return MIFWT_ERR_BADARG;
   }
-  if (d->ndim > 2 || d->filt_len > 20 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64)) return 0;
-  const int last = d->ndim;
-  if (d->sig_stride[last] != 1 || d->approx_stride[last] != 1 || d->detail_stride[last] != 1) return 0;
-  int64_t tiles = d->batch;
-  for (int ax = 0; ax < d->ndim; ++ax) {
-    if (d->coef_extent[ax] > (1 << 29)) return 0;
-    tiles *= (d->coef_extent[ax] + 7) / 8;
-  }
-  if (tiles > INT32_MAX) return 0;
-  return 1;
+  return fused_envelope(d);
 }
 
 template <typename T, int L>
 int launch_fused(const mifwt_level_desc* d, int ext_mode, int adjoint, const void* const* in, void* const* out, const double* lo,
                  const double* hi, hipStream_t stream) {
-  constexpr int E = ExtVec<T>::E;
-  static_assert(FwdGeo<T, L>::LDS2 <= 65536 && AdjGeo<T, L>::LDS2 <= 65536, "tile does not fit the default LDS allowance");
+  typedef FwdGeo<T, L> FG;
+  typedef AdjGeo<T, L> AG;
+  static_assert(FG::LDS2 <= 65536 && AG::LDS2 <= 65536, "tile does not fit the default LDS allowance");
   ExtArgs<T, L> a;
-  const int nd = d->ndim, nb = 1 << nd;
-  for (int s = 0; s < 4; ++s) {
-    a.in[s] = nullptr;
-    a.out[s] = nullptr;
-  }
-  for (int s = 0; s < (adjoint ? nb : 1); ++s) a.in[s] = in[s];
-  for (int s = 0; s < (adjoint ? 1 : nb); ++s) a.out[s] = out[s];
-  a.sig_bs = d->sig_stride[0];
-  a.a_bs = d->approx_stride[0];
-  a.d_bs = d->detail_stride[0];
-  a.sig_rs = nd == 2 ? d->sig_stride[1] : 0;
-  a.a_rs = nd == 2 ? d->approx_stride[1] : 0;
-  a.d_rs = nd == 2 ? d->detail_stride[1] : 0;
-  a.n_r = nd == 2 ? (int)d->sig_extent[0] : 1;
-  a.m_r = nd == 2 ? (int)d->coef_extent[0] : 1;
-  a.n_c = (int)d->sig_extent[nd - 1];
-  a.m_c = (int)d->coef_extent[nd - 1];
+  fill_level_args(a, d, adjoint, in, out, lo, hi, Vec16<T>::E);
   a.mode = ext_mode;
-  const void* sig = adjoint ? out[0] : in[0];
-  a.sig_vec = aligned16(sig) && a.sig_bs % E == 0 && a.sig_rs % E == 0;
-  a.coef_vec = a.a_bs % E == 0 && a.d_bs % E == 0 && a.a_rs % E == 0 && a.d_rs % E == 0;
-  for (int s = 0; s < nb; ++s) a.coef_vec = a.coef_vec && aligned16(adjoint ? in[s] : (const void*)out[s]);
-  for (int t = 0; t < L; ++t) {
-    a.lo[t] = (T)lo[t];
-    a.hi[t] = (T)hi[t];
-  }
   if (d->batch == 0) return MIFWT_OK;
-  int64_t grid;
-  if (nd == 2) {
-    a.tiles_c = adjoint ? (a.n_c + AdjGeo<T, L>::TSC - 1) / AdjGeo<T, L>::TSC : (a.m_c + FwdGeo<T, L>::TC - 1) / FwdGeo<T, L>::TC;
-    a.tiles_r = adjoint ? (a.n_r + AdjGeo<T, L>::TSR - 1) / AdjGeo<T, L>::TSR : (a.m_r + FwdGeo<T, L>::TR - 1) / FwdGeo<T, L>::TR;
-    grid = (int64_t)a.tiles_c * a.tiles_r * d->batch;
-  } else {
-    a.tiles_c = adjoint ? (a.n_c + AdjGeo<T, L>::TS1 - 1) / AdjGeo<T, L>::TS1 : (a.m_c + FwdGeo<T, L>::TC1 - 1) / FwdGeo<T, L>::TC1;
-    a.tiles_r = 1;
-    grid = (int64_t)a.tiles_c * d->batch;
-  }
-  if (grid > INT32_MAX) return MIFWT_ERR_UNSUPPORTED;
+  const int nd = d->ndim;
+  // analysis cuts the coefficients, the adjoint the samples
+  const int tcw = nd == 2 ? (adjoint ? AG::TSC : FG::TC) : (adjoint ? AG::TS1 : FG::TC1);
+  const int64_t grid = adjoint ? cut_tiles(a, a.n_c, a.n_r, tcw, AG::TSR, d->batch) : cut_tiles(a, a.m_c, a.m_r, tcw, FG::TR, d->batch);
+  if (grid < 0) return MIFWT_ERR_UNSUPPORTED;
   const dim3 g((unsigned)grid), blk(256);
   if (nd == 2) {
     if (adjoint)
@@ -585,32 +462,15 @@ int launch_fused(const mifwt_level_desc* d, int ext_mode, int adjoint, const voi
 template <typename T>
 int dispatch_len(const mifwt_level_desc* d, int ext_mode, int adjoint, const void* const* in, void* const* out, const double* lo,
                  const double* hi, hipStream_t stream) {
-  switch (d->filt_len) {
-#define MIFWT_EXT_CASE(LEN) \
-  case LEN: return launch_fused<T, LEN>(d, ext_mode, adjoint, in, out, lo, hi, stream);
-    MIFWT_EXT_CASE(2)
-    MIFWT_EXT_CASE(4)
-    MIFWT_EXT_CASE(6)
-    MIFWT_EXT_CASE(8)
-    MIFWT_EXT_CASE(10)
-    MIFWT_EXT_CASE(12)
-    MIFWT_EXT_CASE(14)
-    MIFWT_EXT_CASE(16)
-    MIFWT_EXT_CASE(18)
-    MIFWT_EXT_CASE(20)
-#undef MIFWT_EXT_CASE
-    default: return MIFWT_ERR_UNSUPPORTED;
-  }
+  return for_even_len(d->filt_len,
+                      [&](auto len) { return launch_fused<T, decltype(len)::value>(d, ext_mode, adjoint, in, out, lo, hi, stream); });
 }
 
 int ext_level(const mifwt_level_desc* d, int ext_mode, int adjoint, const void* const* in, void* const* out, const double* lo,
               const double* hi, void* stream) {
   const int ok = fused_check(d, ext_mode);
   if (ok < 0) return ok;
-  if (!lo || !hi) return MIFWT_ERR_BADARG;
-  for (int s = 0; s < (1 << (d->ndim > 2 ? 0 : d->ndim)); ++s)
-    if (!(adjoint ? in[s] : (const void*)out[s])) return MIFWT_ERR_BADARG;
-  if (!(adjoint ? (const void*)out[0] : in[0])) return MIFWT_ERR_BADARG;
+  if (const int bad = level_pointers(d, adjoint, in, out, lo, hi)) return bad;
   if (!ok) return MIFWT_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return d->dtype == MIFWT_F32 ? dispatch_len<float>(d, ext_mode, adjoint, in, out, lo, hi, st)
@@ -620,47 +480,17 @@ int ext_level(const mifwt_level_desc* d, int ext_mode, int adjoint, const void* 
 int ext_axis(int adjoint, int ext_mode, int dtype, int filt_len, int64_t outer, int64_t n, int64_t inner, const void* in0, const void* in1,
              void* out0, void* out1, const int64_t* sig_s, const int64_t* lo_s, const int64_t* hi_s, const double* lo, const double* hi,
              void* stream) {
-  if (!in0 || !out0 || (adjoint ? !in1 : !out1) || !sig_s || !lo_s || !hi_s || !lo || !hi || !mode_ok(ext_mode)) return MIFWT_ERR_BADARG;
-  if (filt_len < 2 || (filt_len & 1) || filt_len > MIFWT_MAX_FILT || outer < 0 || inner < 0 || n < 1) return MIFWT_ERR_BADARG;
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return is_storage16(dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
-  if (n > INT32_MAX / 4) return MIFWT_ERR_UNSUPPORTED;
-  AxisArgs a;
-  a.in0 = in0;
-  a.in1 = in1;
-  a.out0 = out0;
-  a.out1 = out1;
-  for (int i = 0; i < 3; ++i) {
-    a.sig_s[i] = sig_s[i];
-    a.lo_s[i] = lo_s[i];
-    a.hi_s[i] = hi_s[i];
-  }
-  a.outer = outer;
-  a.inner = inner;
-  a.n = (int)n;
-  a.m = (int)((n + filt_len - 1) / 2);
-  a.filt_len = filt_len;
+  if (!mode_ok(ext_mode)) return MIFWT_ERR_BADARG;
+  if (const int bad = axis_check(adjoint, dtype, filt_len, outer, n, inner, in0, in1, out0, out1, sig_s, lo_s, hi_s, lo, hi)) return bad;
+  ExtAxisArgs a;
+  if (const int bad = fill_axis_args(a, filt_len, outer, n, (n + filt_len - 1) / 2, inner, in0, in1, out0, out1, sig_s, lo_s, hi_s, lo, hi))
+    return bad;
   a.mode = ext_mode;
-  for (int t = 0; t < MIFWT_MAX_FILT; ++t) {
-    a.lo[t] = t < filt_len ? lo[t] : 0.0;
-    a.hi[t] = t < filt_len ? hi[t] : 0.0;
-  }
   const int64_t total = outer * (adjoint ? n : (int64_t)a.m) * inner;
   if (total == 0) return MIFWT_OK;
-  const int64_t blocks = (total + 255) / 256;
-  const dim3 g((unsigned)(blocks < 65536 ? blocks : 65536)), blk(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == MIFWT_F32) {
-    if (adjoint)
-      hipLaunchKernelGGL((ext_axis_kernel<float, true>), g, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((ext_axis_kernel<float, false>), g, blk, 0, st, a);
-  } else {
-    if (adjoint)
-      hipLaunchKernelGGL((ext_axis_kernel<double, true>), g, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((ext_axis_kernel<double, false>), g, blk, 0, st, a);
-  }
-  if (hipGetLastError() != hipSuccess) return MIFWT_ERR_LAUNCH;
+  const int rc = launch_axis(dtype, adjoint, total, 65536, stream, a, ext_axis_kernel<float, false>, ext_axis_kernel<float, true>,
+                             ext_axis_kernel<double, false>, ext_axis_kernel<double, true>);
+  if (rc != MIFWT_OK) return rc;
   count_launch(adjoint ? MIFWT_KID_EXT_AXIS_ADJ : MIFWT_KID_EXT_AXIS_FWD);
   return MIFWT_OK;
 }
@@ -677,30 +507,22 @@ int mifwt_ext_supported(const mifwt_level_desc* desc, int ext_mode, int directio
 }
 
 int mifwt_ext_kernel_id(const mifwt_level_desc* desc, int ext_mode, int direction) {
-  const int ok = mifwt_ext_supported(desc, ext_mode, direction);
-  if (ok < 0) return ok;
-  return ok ? (direction ? MIFWT_KID_EXT_ADJ : MIFWT_KID_EXT_FWD) : MIFWT_ERR_UNSUPPORTED;
+  return mifwt::kernel_id_answer(mifwt_ext_supported(desc, ext_mode, direction), direction, MIFWT_KID_EXT_FWD, MIFWT_KID_EXT_ADJ);
 }
 
 int mifwt_ext_fwd(const mifwt_level_desc* desc, int ext_mode, const void* x, void* approx, void* const* details, const double* lo,
                   const double* hi, void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
   const void* in[4] = {x, nullptr, nullptr, nullptr};
-  void* out[4] = {approx, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) out[s] = details[s - 1];
+  void* out[4];
+  if (const int bad = mifwt::pack_bands<void*>(desc, approx, details, out)) return bad;
   return mifwt::ext_level(desc, ext_mode, 0, in, out, lo, hi, stream);
 }
 
 int mifwt_ext_adj(const mifwt_level_desc* desc, int ext_mode, const void* g_approx, const void* const* g_details, void* g_x, const double* lo,
                   const double* hi, void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !g_details) return MIFWT_ERR_BADARG;
-  const void* in[4] = {g_approx, nullptr, nullptr, nullptr};
+  const void* in[4];
   void* out[4] = {g_x, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) in[s] = g_details[s - 1];
+  if (const int bad = mifwt::pack_bands<const void*>(desc, g_approx, g_details, in)) return bad;
   return mifwt::ext_level(desc, ext_mode, 1, in, out, lo, hi, stream);
 }
 

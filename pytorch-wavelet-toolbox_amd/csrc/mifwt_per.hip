@@ -16,26 +16,15 @@
 // The parity p of a synthesis sample selects the taps, so every lane computes whole pairs (columns) or whole vectors (rows) of samples
 // and all tap indices are compile-time: the taps stay in registers.
 // Everything else (L > 20, any strides, the depth axis of a 3-D level) runs per_axis_kernel: one thread per output, run-time tap loop.
-#include "mifwt_common.h"
+// Shared with the other fused-level units, from mifwt_level_tile.h: the 16-byte vectors, the row pass over the aligned window (left
+// reach H), the tap step of the column pass and the band stores, the common kernel arguments and their fill, the tile cut, the
+// descriptor prelude and envelope, the length dispatch, the packing of the level entries and the axis-pass arguments and launcher.
+// Here: the index map, the staging, the geometry, the synthesis kernels and the launches.
+#include "mifwt_level_tile.h"
 
 namespace mifwt {
 
 namespace {
-
-template <typename T>
-struct PerVec;
-template <>
-struct PerVec<float> {
-  static constexpr int E = 4;
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <>
-struct PerVec<double> {
-  static constexpr int E = 2;
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-
-constexpr int rup(int v, int m) { return (v + m - 1) / m * m; }
 
 // index i of the periodic extension of `m` entries (any i)
 __device__ __forceinline__ int wrap(int i, int m) {
@@ -52,67 +41,44 @@ __device__ __forceinline__ int per_map(int i, int n, int n2) {
 // ---- tile geometry (compile time; static LDS below 64 KB, at least two workgroups per CU) ----------------------------------------------
 template <typename T, int L>
 struct FwdGeo {
-  static constexpr int E = PerVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int H = L / 2 - 1;
   static constexpr int TC = 16 * E;                   // coefficient columns per tile: 16 lanes x one 16-byte store
   static constexpr int TR = 16;                       // coefficient rows per tile: one column-pass item per thread
-  static constexpr int PAD = rup(H, E);               // staged columns left of sample 2 mc0 (keeps the staged vectors aligned)
-  static constexpr int OFF = PAD - H;                 // window of output 0 starts at staged column OFF
-  static constexpr int NV = (OFF + 2 * E + L - 2 + E - 1) / E;  // 16-byte pieces of the window of E outputs
-  static constexpr int WC = rup(PAD + 2 * TC + L / 2 - 1, E);
+  static constexpr int PAD = RowWindow<T, L, H>::PAD;  // staged columns left of sample 2 mc0 (keeps the staged vectors aligned)
+  static constexpr int WC = round_up(PAD + 2 * TC + L / 2 - 1, E);
   static constexpr int XP = WC + E;                   // pitch of the staged window (a lane's last piece may end inside the pad)
   static constexpr int WR = 2 * TR + L - 2;
   static constexpr int HP = TC + E;                   // pitch of the row-filtered planes: one access width against bank conflicts
   static constexpr int TC1 = 256 * E;                 // 1-D: coefficients per workgroup
-  static constexpr int WC1 = rup(PAD + 2 * TC1 + L / 2 - 1, E);
+  static constexpr int WC1 = round_up(PAD + 2 * TC1 + L / 2 - 1, E);
   static constexpr int LDS2 = (WR * XP + 2 * WR * HP) * (int)sizeof(T);
 };
 
 template <typename T, int L>
 struct InvGeo {
-  static constexpr int E = PerVec<T>::E;
+  static constexpr int E = Vec16<T>::E;
   static constexpr int H = L / 2 - 1;
   static constexpr int TQC = 16 * E;                  // coefficient columns per tile (2 TQC samples)
   static constexpr int TQ = L <= 12 ? 16 : 8;         // coefficient rows per tile (2 TQ sample rows)
-  static constexpr int PMC = rup(H, E);               // staged coefficients left of column qc0
-  static constexpr int WCM = rup(PMC + TQC + H, E);
+  static constexpr int PMC = round_up(H, E);          // staged coefficients left of column qc0
+  static constexpr int WCM = round_up(PMC + TQC + H, E);
   static constexpr int WRM = TQ + 2 * H;
   static constexpr int WL = H + (E + L / 2 - 2) / 2 + 1;  // coefficients per band behind E consecutive samples
   static constexpr int TQ1 = 128 * E;                 // 1-D: coefficients per workgroup
-  static constexpr int WCM1 = rup(PMC + TQ1 + H, E);
+  static constexpr int WCM1 = round_up(PMC + TQ1 + H, E);
   static constexpr int LDS2 = (4 * WRM * WCM + 2 * 2 * TQ * WCM) * (int)sizeof(T);
 };
 
+// analysis: dec_* taps and the real signal extents;  synthesis: rec_* taps;  coefficient extents = ceil(n / 2)
 template <typename T, int L>
-struct PerArgs {
-  const void* in[4];  // analysis: in[0] = x;  synthesis: the 2^ndim bands
-  void* out[4];       // analysis: the bands;  synthesis: out[0] = y
-  int64_t sig_bs, sig_rs;          // signal side: batch / row stride (elements; samples contiguous).  1-D: rows = batch
-  int64_t a_bs, a_rs, d_bs, d_rs;  // band 0 / bands 1..: batch / row strides
-  int n_r, n_c;                    // real signal extents (1-D: n_r = 1)
-  int m_r, m_c;                    // coefficient extents = ceil(n / 2)
-  int sig_vec, coef_vec;           // 16-byte accesses allowed on the signal / coefficient side
-  int tiles_c, tiles_r;
-  T lo[L], hi[L];                  // PyWavelets order: dec_* (analysis) / rec_* (synthesis)
-};
-
-template <typename T>
-__device__ __forceinline__ void store_vec(T* p, const typename PerVec<T>::type& v, int valid, bool vec_ok) {
-  constexpr int E = PerVec<T>::E;
-  if (vec_ok && valid >= E) {
-    *reinterpret_cast<typename PerVec<T>::type*>(p) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-      if (e < valid) p[e] = v[e];
-  }
-}
+struct PerArgs : LevelArgs<T, L> {};
 
 // E staged samples of one row from global column g0 (a multiple of E): `mapped` = through the index map
 template <typename T>
 __device__ __forceinline__ void stage_sig(T* dst, const T* __restrict__ row, int g0, int n, int n2, bool vec_ok, bool mapped) {
-  constexpr int E = PerVec<T>::E;
-  typedef typename PerVec<T>::type V;
+  constexpr int E = Vec16<T>::E;
+  typedef typename Vec16<T>::type V;
   if (vec_ok && (!mapped || (g0 >= 0 && g0 + E <= n))) {
     *reinterpret_cast<V*>(dst) = *reinterpret_cast<const V*>(row + g0);
   } else {
@@ -124,8 +90,8 @@ __device__ __forceinline__ void stage_sig(T* dst, const T* __restrict__ row, int
 // E staged coefficients of one band row from column g0 (a multiple of E), periodic with period m
 template <typename T>
 __device__ __forceinline__ void stage_coef(T* dst, const T* __restrict__ row, int g0, int m, bool vec_ok, bool mapped) {
-  constexpr int E = PerVec<T>::E;
-  typedef typename PerVec<T>::type V;
+  constexpr int E = Vec16<T>::E;
+  typedef typename Vec16<T>::type V;
   if (vec_ok && (!mapped || (g0 >= 0 && g0 + E <= m))) {
     *reinterpret_cast<V*>(dst) = *reinterpret_cast<const V*>(row + g0);
   } else {
@@ -134,38 +100,11 @@ __device__ __forceinline__ void stage_coef(T* dst, const T* __restrict__ row, in
   }
 }
 
-// E consecutive outputs of both filters from a staged row; `p` = 16-byte aligned LDS address of staged column 2 * (first output)
-template <typename T, int L>
-__device__ __forceinline__ void analysis_run(const T* p, const T (&flo)[L], const T (&fhi)[L], typename PerVec<T>::type& lo,
-                                             typename PerVec<T>::type& hi) {
-  typedef FwdGeo<T, L> G;
-  typedef typename PerVec<T>::type V;
-  constexpr int E = G::E, OFF = G::OFF, NV = G::NV;
-  T w[NV * E];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const V v = *reinterpret_cast<const V*>(p + i * E);
-#pragma unroll
-    for (int e = 0; e < E; ++e) w[i * E + e] = v[e];
-  }
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    T sl = T(0), sh = T(0);
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-      sl = fma(flo[L - 1 - k], w[OFF + 2 * e + k], sl);
-      sh = fma(fhi[L - 1 - k], w[OFF + 2 * e + k], sh);
-    }
-    lo[e] = sl;
-    hi[e] = sh;
-  }
-}
-
 // E consecutive samples (first one even) from the staged rows of the two bands; r0 / r1 point at the coefficient k0(first sample) - H
 template <typename T, int L>
-__device__ __forceinline__ typename PerVec<T>::type synthesis_run(const T* r0, const T* r1, const T (&rlo)[L], const T (&rhi)[L]) {
+__device__ __forceinline__ typename Vec16<T>::type synthesis_run(const T* r0, const T* r1, const T (&rlo)[L], const T (&rhi)[L]) {
   typedef InvGeo<T, L> G;
-  typedef typename PerVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, H = G::H, WL = G::WL;
   T w0[WL], w1[WL];
 #pragma unroll
@@ -192,7 +131,7 @@ __device__ __forceinline__ typename PerVec<T>::type synthesis_run(const T* r0, c
 template <typename T, int L>
 __global__ void __launch_bounds__(256) per_fwd2_kernel(const PerArgs<T, L> a) {
   typedef FwdGeo<T, L> G;
-  typedef typename PerVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC, TR = G::TR, H = G::H, WC = G::WC, WR = G::WR, XP = G::XP, HP = G::HP;
   __shared__ __attribute__((aligned(16))) T xs[WR * XP];
   __shared__ __attribute__((aligned(16))) T hs[2 * WR * HP];
@@ -217,7 +156,7 @@ __global__ void __launch_bounds__(256) per_fwd2_kernel(const PerArgs<T, L> a) {
   for (int i = tid; i < WR * (TC / E); i += 256) {
     const int r = i / (TC / E), cg = i - r * (TC / E);
     V lo, hi;
-    analysis_run<T, L>(xs + r * XP + 2 * cg * E, a.lo, a.hi, lo, hi);
+    window_run<T, L, H>(xs + r * XP + 2 * cg * E, a.lo, a.hi, lo, hi);
     *reinterpret_cast<V*>(hs + r * HP + cg * E) = lo;
     *reinterpret_cast<V*>(hs + (WR + r) * HP + cg * E) = hi;
   }
@@ -231,22 +170,8 @@ __global__ void __launch_bounds__(256) per_fwd2_kernel(const PerArgs<T, L> a) {
     const T* hl0 = hs + (2 * ro) * HP + cg * E;
     const T* hh0 = hl0 + WR * HP;
 #pragma unroll
-    for (int k = 0; k < L; ++k) {
-      const V vl = *reinterpret_cast<const V*>(hl0 + k * HP);
-      const V vh = *reinterpret_cast<const V*>(hh0 + k * HP);
-      const T cl = a.lo[L - 1 - k], ch = a.hi[L - 1 - k];
-      ll += cl * vl;
-      lh += cl * vh;
-      hl += ch * vl;
-      hh += ch * vh;
-    }
-    const int valid = a.m_c - mc;
-    const int64_t oa = (int64_t)b * a.a_bs + (int64_t)m * a.a_rs + mc;
-    const int64_t od = (int64_t)b * a.d_bs + (int64_t)m * a.d_rs + mc;
-    store_vec<T>(static_cast<T*>(a.out[0]) + oa, ll, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[1]) + od, lh, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[2]) + od, hl, valid, a.coef_vec);
-    store_vec<T>(static_cast<T*>(a.out[3]) + od, hh, valid, a.coef_vec);
+    for (int k = 0; k < L; ++k) column_tap<T>(hl0 + k * HP, hh0 + k * HP, a.lo[L - 1 - k], a.hi[L - 1 - k], ll, lh, hl, hh);
+    store_bands<T, L>(a, b, m, mc, ll, lh, hl, hh);
   }
 }
 
@@ -254,7 +179,7 @@ __global__ void __launch_bounds__(256) per_fwd2_kernel(const PerArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) per_fwd1_kernel(const PerArgs<T, L> a) {
   typedef FwdGeo<T, L> G;
-  typedef typename PerVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, TC = G::TC1, WC = G::WC1;
   __shared__ __attribute__((aligned(16))) T xs[WC + E];
   const int tid = threadIdx.x;
@@ -269,7 +194,7 @@ __global__ void __launch_bounds__(256) per_fwd1_kernel(const PerArgs<T, L> a) {
   const int mc = mc0 + tid * E;
   if (mc >= a.m_c) return;
   V lo, hi;
-  analysis_run<T, L>(xs + 2 * tid * E, a.lo, a.hi, lo, hi);
+  window_run<T, L, G::H>(xs + 2 * tid * E, a.lo, a.hi, lo, hi);
   store_vec<T>(static_cast<T*>(a.out[0]) + (int64_t)b * a.a_bs + mc, lo, a.m_c - mc, a.coef_vec);
   store_vec<T>(static_cast<T*>(a.out[1]) + (int64_t)b * a.d_bs + mc, hi, a.m_c - mc, a.coef_vec);
 }
@@ -278,7 +203,7 @@ __global__ void __launch_bounds__(256) per_fwd1_kernel(const PerArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) per_inv2_kernel(const PerArgs<T, L> a) {
   typedef InvGeo<T, L> G;
-  typedef typename PerVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, H = G::H, TQ = G::TQ, TQC = G::TQC, WCM = G::WCM, WRM = G::WRM, PMC = G::PMC;
   __shared__ __attribute__((aligned(16))) T bs[4 * WRM * WCM];
   __shared__ __attribute__((aligned(16))) T ts[2 * 2 * TQ * WCM];
@@ -332,7 +257,7 @@ __global__ void __launch_bounds__(256) per_inv2_kernel(const PerArgs<T, L> a) {
 template <typename T, int L>
 __global__ void __launch_bounds__(256) per_inv1_kernel(const PerArgs<T, L> a) {
   typedef InvGeo<T, L> G;
-  typedef typename PerVec<T>::type V;
+  typedef typename Vec16<T>::type V;
   constexpr int E = G::E, H = G::H, TQ1 = G::TQ1, WCM = G::WCM1, PMC = G::PMC;
   __shared__ __attribute__((aligned(16))) T bs[2 * WCM];
   const int tid = threadIdx.x;
@@ -355,19 +280,8 @@ __global__ void __launch_bounds__(256) per_inv1_kernel(const PerArgs<T, L> a) {
 }
 
 // ---- one axis of [outer, n, inner] arrays: any even L <= MIFWT_MAX_FILT, any strides -----------------------------------------------------------
-struct AxisArgs {
-  const void* in0;  // analysis: x       synthesis: lo
-  const void* in1;  //                   synthesis: hi
-  void* out0;       // analysis: lo      synthesis: y
-  void* out1;       // analysis: hi
-  int64_t sig_s[3], lo_s[3], hi_s[3];  // (outer, axis, inner) strides in elements
-  int64_t outer, inner;
-  int n, m, filt_len;
-  double lo[MIFWT_MAX_FILT], hi[MIFWT_MAX_FILT];
-};
-
 template <typename T, bool INVERSE>
-__global__ void __launch_bounds__(256) per_axis_kernel(const AxisArgs a) {
+__global__ void __launch_bounds__(256) per_axis_kernel(const AxisArgsBase a) {
   const int L = a.filt_len, M = a.m, N2 = 2 * a.m;
   const int64_t len = INVERSE ? a.n : M;
   const int64_t total = a.outer * len * a.inner;
@@ -403,75 +317,27 @@ __global__ void __launch_bounds__(256) per_axis_kernel(const AxisArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // 0 = not served by the fused kernels, MIFWT_ERR_BADARG = inconsistent, 1 = served
 int fused_check(const mifwt_level_desc* d) {
-  if (!d) return MIFWT_ERR_BADARG;
-  if (d->ndim < 1 || d->ndim > MIFWT_MAX_NDIM || d->filt_len < 2 || d->filt_len > MIFWT_MAX_FILT || (d->filt_len & 1) || d->batch < 0)
-    return MIFWT_ERR_BADARG;
-  if (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64 && !is_storage16(d->dtype)) return MIFWT_ERR_BADARG;
+  if (const int bad = desc_prelude(d)) return bad;
   for (int ax = 0; ax < d->ndim; ++ax) {
     const int64_t n = d->sig_extent[ax], m = d->coef_extent[ax];
     if (n < 1 || m != (n + 1) / 2) return MIFWT_ERR_BADARG;
   }
-  if (d->ndim > 2 || d->filt_len > 20 || (d->dtype != MIFWT_F32 && d->dtype != MIFWT_F64)) return 0;
-  const int last = d->ndim;
-  if (d->sig_stride[last] != 1 || d->approx_stride[last] != 1 || d->detail_stride[last] != 1) return 0;
-  int64_t tiles = d->batch;
-  for (int ax = 0; ax < d->ndim; ++ax) {
-    if (d->coef_extent[ax] > (1 << 29)) return 0;
-    tiles *= (d->coef_extent[ax] + 7) / 8;
-  }
-  if (tiles > INT32_MAX) return 0;
-  return 1;
+  return fused_envelope(d);
 }
 
 template <typename T, int L>
 int launch_fused(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
                  hipStream_t stream) {
-  constexpr int E = PerVec<T>::E;
   static_assert(FwdGeo<T, L>::LDS2 <= 65536 && InvGeo<T, L>::LDS2 <= 65536, "tile does not fit the default LDS allowance");
   PerArgs<T, L> a;
-  const int nd = d->ndim, nb = 1 << nd;
-  for (int s = 0; s < 4; ++s) {
-    a.in[s] = nullptr;
-    a.out[s] = nullptr;
-  }
-  for (int s = 0; s < (inverse ? nb : 1); ++s) a.in[s] = in[s];
-  for (int s = 0; s < (inverse ? 1 : nb); ++s) a.out[s] = out[s];
-  a.sig_bs = d->sig_stride[0];
-  a.a_bs = d->approx_stride[0];
-  a.d_bs = d->detail_stride[0];
-  a.sig_rs = nd == 2 ? d->sig_stride[1] : 0;
-  a.a_rs = nd == 2 ? d->approx_stride[1] : 0;
-  a.d_rs = nd == 2 ? d->detail_stride[1] : 0;
-  a.n_r = nd == 2 ? (int)d->sig_extent[0] : 1;
-  a.m_r = nd == 2 ? (int)d->coef_extent[0] : 1;
-  a.n_c = (int)d->sig_extent[nd - 1];
-  a.m_c = (int)d->coef_extent[nd - 1];
-  const void* sig = inverse ? out[0] : in[0];
-  a.sig_vec = aligned16(sig) && a.sig_bs % E == 0 && a.sig_rs % E == 0;
-  a.coef_vec = a.a_bs % E == 0 && a.d_bs % E == 0 && a.a_rs % E == 0 && a.d_rs % E == 0;
-  for (int s = 0; s < nb; ++s) a.coef_vec = a.coef_vec && aligned16(inverse ? in[s] : (const void*)out[s]);
-  for (int t = 0; t < L; ++t) {
-    a.lo[t] = (T)lo[t];
-    a.hi[t] = (T)hi[t];
-  }
+  fill_level_args(a, d, inverse, in, out, lo, hi, Vec16<T>::E);
   if (d->batch == 0) return MIFWT_OK;
-  int64_t grid;
-  if (nd == 2) {
-    const int tcw = inverse ? InvGeo<T, L>::TQC : FwdGeo<T, L>::TC, trw = inverse ? InvGeo<T, L>::TQ : FwdGeo<T, L>::TR;
-    a.tiles_c = (a.m_c + tcw - 1) / tcw;
-    a.tiles_r = (a.m_r + trw - 1) / trw;
-    grid = (int64_t)a.tiles_c * a.tiles_r * d->batch;
-  } else {
-    const int tcw = inverse ? InvGeo<T, L>::TQ1 : FwdGeo<T, L>::TC1;
-    a.tiles_c = (a.m_c + tcw - 1) / tcw;
-    a.tiles_r = 1;
-    grid = (int64_t)a.tiles_c * d->batch;
-  }
-  if (grid > INT32_MAX) return MIFWT_ERR_UNSUPPORTED;
+  const int nd = d->ndim;
+  const int tcw = nd == 2 ? (inverse ? InvGeo<T, L>::TQC : FwdGeo<T, L>::TC) : (inverse ? InvGeo<T, L>::TQ1 : FwdGeo<T, L>::TC1);
+  const int64_t grid = cut_tiles(a, a.m_c, a.m_r, tcw, inverse ? InvGeo<T, L>::TQ : FwdGeo<T, L>::TR, d->batch);
+  if (grid < 0) return MIFWT_ERR_UNSUPPORTED;
   const dim3 g((unsigned)grid), blk(256);
   if (nd == 2) {
     if (inverse)
@@ -492,32 +358,14 @@ int launch_fused(const mifwt_level_desc* d, int inverse, const void* const* in, 
 template <typename T>
 int dispatch_len(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
                  hipStream_t stream) {
-  switch (d->filt_len) {
-#define MIFWT_PER_CASE(LEN) \
-  case LEN: return launch_fused<T, LEN>(d, inverse, in, out, lo, hi, stream);
-    MIFWT_PER_CASE(2)
-    MIFWT_PER_CASE(4)
-    MIFWT_PER_CASE(6)
-    MIFWT_PER_CASE(8)
-    MIFWT_PER_CASE(10)
-    MIFWT_PER_CASE(12)
-    MIFWT_PER_CASE(14)
-    MIFWT_PER_CASE(16)
-    MIFWT_PER_CASE(18)
-    MIFWT_PER_CASE(20)
-#undef MIFWT_PER_CASE
-    default: return MIFWT_ERR_UNSUPPORTED;
-  }
+  return for_even_len(d->filt_len, [&](auto len) { return launch_fused<T, decltype(len)::value>(d, inverse, in, out, lo, hi, stream); });
 }
 
 int per_level(const mifwt_level_desc* d, int inverse, const void* const* in, void* const* out, const double* lo, const double* hi,
               void* stream) {
   const int ok = fused_check(d);
   if (ok < 0) return ok;
-  if (!lo || !hi) return MIFWT_ERR_BADARG;
-  for (int s = 0; s < (1 << (d->ndim > 2 ? 0 : d->ndim)); ++s)
-    if (!(inverse ? in[s] : (const void*)out[s])) return MIFWT_ERR_BADARG;
-  if (!(inverse ? (const void*)out[0] : in[0])) return MIFWT_ERR_BADARG;
+  if (const int bad = level_pointers(d, inverse, in, out, lo, hi)) return bad;
   if (!ok) return MIFWT_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return d->dtype == MIFWT_F32 ? dispatch_len<float>(d, inverse, in, out, lo, hi, st) : dispatch_len<double>(d, inverse, in, out, lo, hi, st);
@@ -525,46 +373,14 @@ int per_level(const mifwt_level_desc* d, int inverse, const void* const* in, voi
 
 int per_axis(int inverse, int dtype, int filt_len, int64_t outer, int64_t n, int64_t inner, const void* in0, const void* in1, void* out0,
              void* out1, const int64_t* sig_s, const int64_t* lo_s, const int64_t* hi_s, const double* lo, const double* hi, void* stream) {
-  if (!in0 || !out0 || (inverse ? !in1 : !out1) || !sig_s || !lo_s || !hi_s || !lo || !hi) return MIFWT_ERR_BADARG;
-  if (filt_len < 2 || (filt_len & 1) || filt_len > MIFWT_MAX_FILT || outer < 0 || inner < 0 || n < 1) return MIFWT_ERR_BADARG;
-  if (dtype != MIFWT_F32 && dtype != MIFWT_F64) return is_storage16(dtype) ? MIFWT_ERR_UNSUPPORTED : MIFWT_ERR_BADARG;
-  if (n > INT32_MAX / 4) return MIFWT_ERR_UNSUPPORTED;
-  AxisArgs a;
-  a.in0 = in0;
-  a.in1 = in1;
-  a.out0 = out0;
-  a.out1 = out1;
-  for (int i = 0; i < 3; ++i) {
-    a.sig_s[i] = sig_s[i];
-    a.lo_s[i] = lo_s[i];
-    a.hi_s[i] = hi_s[i];
-  }
-  a.outer = outer;
-  a.inner = inner;
-  a.n = (int)n;
-  a.m = (int)((n + 1) / 2);
-  a.filt_len = filt_len;
-  for (int t = 0; t < MIFWT_MAX_FILT; ++t) {
-    a.lo[t] = t < filt_len ? lo[t] : 0.0;
-    a.hi[t] = t < filt_len ? hi[t] : 0.0;
-  }
+  if (const int bad = axis_check(inverse, dtype, filt_len, outer, n, inner, in0, in1, out0, out1, sig_s, lo_s, hi_s, lo, hi)) return bad;
+  AxisArgsBase a;
+  if (const int bad = fill_axis_args(a, filt_len, outer, n, (n + 1) / 2, inner, in0, in1, out0, out1, sig_s, lo_s, hi_s, lo, hi)) return bad;
   const int64_t total = outer * (inverse ? n : (int64_t)a.m) * inner;
   if (total == 0) return MIFWT_OK;
-  const int64_t blocks = (total + 255) / 256;
-  const dim3 g((unsigned)(blocks < 65536 ? blocks : 65536)), blk(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == MIFWT_F32) {
-    if (inverse)
-      hipLaunchKernelGGL((per_axis_kernel<float, true>), g, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((per_axis_kernel<float, false>), g, blk, 0, st, a);
-  } else {
-    if (inverse)
-      hipLaunchKernelGGL((per_axis_kernel<double, true>), g, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((per_axis_kernel<double, false>), g, blk, 0, st, a);
-  }
-  if (hipGetLastError() != hipSuccess) return MIFWT_ERR_LAUNCH;
+  const int rc = launch_axis(dtype, inverse, total, 65536, stream, a, per_axis_kernel<float, false>, per_axis_kernel<float, true>,
+                             per_axis_kernel<double, false>, per_axis_kernel<double, true>);
+  if (rc != MIFWT_OK) return rc;
   count_launch(inverse ? MIFWT_KID_PER_AXIS_INV : MIFWT_KID_PER_AXIS_FWD);
   return MIFWT_OK;
 }
@@ -581,30 +397,22 @@ int mifwt_per_supported(const mifwt_level_desc* desc, int direction) {
 }
 
 int mifwt_per_kernel_id(const mifwt_level_desc* desc, int direction) {
-  const int ok = mifwt_per_supported(desc, direction);
-  if (ok < 0) return ok;
-  return ok ? (direction ? MIFWT_KID_PER_INV : MIFWT_KID_PER_FWD) : MIFWT_ERR_UNSUPPORTED;
+  return mifwt::kernel_id_answer(mifwt_per_supported(desc, direction), direction, MIFWT_KID_PER_FWD, MIFWT_KID_PER_INV);
 }
 
 int mifwt_per_fwd(const mifwt_level_desc* desc, const void* x, void* approx, void* const* details, const double* lo, const double* hi,
                   void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
   const void* in[4] = {x, nullptr, nullptr, nullptr};
-  void* out[4] = {approx, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) out[s] = details[s - 1];
+  void* out[4];
+  if (const int bad = mifwt::pack_bands<void*>(desc, approx, details, out)) return bad;
   return mifwt::per_level(desc, 0, in, out, lo, hi, stream);
 }
 
 int mifwt_per_inv(const mifwt_level_desc* desc, const void* approx, const void* const* details, void* y, const double* lo, const double* hi,
                   void* stream) {
-  if (!desc || desc->ndim < 1 || desc->ndim > MIFWT_MAX_NDIM) return MIFWT_ERR_BADARG;
-  if (desc->ndim <= 2 && !details) return MIFWT_ERR_BADARG;
-  const void* in[4] = {approx, nullptr, nullptr, nullptr};
+  const void* in[4];
   void* out[4] = {y, nullptr, nullptr, nullptr};
-  if (desc->ndim <= 2)
-    for (int s = 1; s < (1 << desc->ndim); ++s) in[s] = details[s - 1];
+  if (const int bad = mifwt::pack_bands<const void*>(desc, approx, details, in)) return bad;
   return mifwt::per_level(desc, 1, in, out, lo, hi, stream);
 }
 

@@ -339,9 +339,11 @@ def test_tile_table_of_the_gpu_tests_is_the_geometry_of_the_source():
                 nest -= 1
         raise AssertionError(e)
 
+    with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_level_tile.h")) as f:
+        shared = f.read()  # (the vector type is shared by every fused-level unit; the row bank takes it from there)
+    assert re.search(r"struct Vec16<float> \{\s*static constexpr int E = 4;", shared) and re.search(r"struct Vec16<double> \{\s*static constexpr int E = 2;", shared)
     with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_bwt_rows.h")) as f:
-        rows = f.read()  # (the vector type is the row bank's, shared by the boundary-wavelet kernels)
-    assert re.search(r"struct BwtVec<float> \{\s*static constexpr int E = 4;", rows) and re.search(r"struct BwtVec<double> \{\s*static constexpr int E = 2;", rows)
+        assert '#include "mifwt_level_tile.h"' in f.read()
     assert K.E == {torch.float32: 4, torch.float64: 2}
     assert K.FUSED == [2, 4, 6, 8] and all("MIFWT_BWT3_CASE(%d)" % flen in src for flen in K.FUSED) and "MIFWT_BWT3_CASE(10)" not in src
     assert "constexpr int kMaxFused3 = 8;" in src

@@ -239,6 +239,39 @@ def test_c_abi_host_side():
     assert lib.mifwt_bwt_inv(ctypes.byref(bad), None, null_details, None, taps, taps, ctypes.byref(tab), None) == BADARG
     strides = (ctypes.c_int64 * 3)(4096, 1, 1)
     assert lib.mifwt_bwt_axis_fwd(F32, 8, 0, 2, 4096, 1, None, strides, None, strides, None, strides, taps, taps, ctypes.byref(tab), None) == BADARG
+    # a null descriptor, then one null pointer at a time on a served descriptor (the table's rows are never read on the host)
+    buf = (ctypes.c_double * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    det, null_det = (ctypes.c_void_p * 3)(p, p, p), (ctypes.c_void_p * 3)(p, None, p)
+    tab, no_rows = ctypes.byref(_bwt.BwtTables(p.value, 2, 2)), ctypes.byref(_bwt.BwtTables(0, 2, 2))
+    assert lib.mifwt_bwt_supported(None, 0) == BADARG
+    assert lib.mifwt_bwt_fwd(None, p, p, det, taps, taps, tab, None) == BADARG
+    assert lib.mifwt_bwt_inv(None, p, det, p, taps, taps, tab, None) == BADARG
+    d2 = _desc(2, F32, 8, 1, [16, 16])
+    for args in ((None, p, det, taps, taps, tab), (p, None, det, taps, taps, tab), (p, p, None, taps, taps, tab), (p, p, null_det, taps, taps, tab),
+                 (p, p, det, None, taps, tab), (p, p, det, taps, None, tab), (p, p, det, taps, taps, None), (p, p, det, taps, taps, no_rows)):
+        assert lib.mifwt_bwt_fwd(ctypes.byref(d2), *args, None) == BADARG, args
+    for args in ((None, det, p, taps, taps, tab), (p, None, p, taps, taps, tab), (p, null_det, p, taps, taps, tab), (p, det, None, taps, taps, tab),
+                 (p, det, p, None, taps, tab), (p, det, p, taps, None, tab), (p, det, p, taps, taps, None), (p, det, p, taps, taps, no_rows)):
+        assert lib.mifwt_bwt_inv(ctypes.byref(d2), *args, None) == BADARG, args
+    # outside the fused envelope with valid pointers: refused, nothing launched (a launch without a device could not answer UNSUPPORTED)
+    long_taps = (ctypes.c_double * 22)()
+    long_tab = ctypes.byref(_bwt.BwtTables(p.value, 5, 5))
+    far = _desc(2, F32, 22, 1, [64, 64])
+    assert lib.mifwt_bwt_fwd(ctypes.byref(far), p, p, det, long_taps, long_taps, long_tab, None) == UNSUPPORTED
+    assert lib.mifwt_bwt_inv(ctypes.byref(far), p, det, p, long_taps, long_taps, long_tab, None) == UNSUPPORTED
+    near = _desc(1, F32, 8, 2, [12])  # L <= N < 2 (L - 1)
+    assert lib.mifwt_bwt_fwd(ctypes.byref(near), p, p, det, taps, taps, tab, None) == UNSUPPORTED
+    # the axis entries: one null at a time (-1), float16 and overlapping ends with valid pointers (-2)
+    st = (ctypes.c_int64 * 3)(16, 1, 1)
+    good = [p, st, p, st, p, st, taps, taps, tab]
+    for entry, head in ((lib.mifwt_bwt_axis_fwd, (8, 0)), (lib.mifwt_bwt_axis_inv, (8,))):
+        for hole in range(len(good)):
+            assert entry(F32, *head, 1, 16, 1, *[None if i == hole else v for i, v in enumerate(good)], None) == BADARG, hole
+        assert entry(F32, *head, 1, 16, 1, *good[:-1], no_rows, None) == BADARG
+        assert entry(F16, *head, 1, 16, 1, *good, None) == UNSUPPORTED
+        assert entry(F32, *head, 1, 12, 1, *good, None) == UNSUPPORTED
+        assert entry(F32, *head, 1, 6, 1, *good, None) == BADARG
     assert OK == 0
 
 
@@ -359,9 +392,11 @@ def test_tile_table_of_the_gpu_kernel_tests_is_the_geometry_of_the_source():
         (expr,) = re.findall(r"static constexpr int %s = ([^;]+);" % name, src)
         return expr.strip()
 
+    with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_level_tile.h")) as f:
+        shared = f.read()  # (the vector type is shared by every fused-level unit; the row bank takes it from there)
+    assert re.search(r"struct Vec16<float> \{\s*static constexpr int E = 4;", shared) and re.search(r"struct Vec16<double> \{\s*static constexpr int E = 2;", shared)
     with open(os.path.join(os.path.dirname(_bwt.__file__), "csrc", "mifwt_bwt_rows.h")) as f:
-        rows = f.read()  # (the vector type is the row bank's, shared by the boundary-wavelet kernels)
-    assert re.search(r"struct BwtVec<float> \{\s*static constexpr int E = 4;", rows) and re.search(r"struct BwtVec<double> \{\s*static constexpr int E = 2;", rows)
+        assert '#include "mifwt_level_tile.h"' in f.read()
     assert K.E == {torch.float32: 4, torch.float64: 2}
     assert (const("TC1"), const("TC"), const("TR")) == ("256 * E", "16 * E", "8")
     assert (const("TQ1"), const("TQ"), const("TQC")) == ("128 * E", "16", "(L <= 12 ? 16 : 8) * E")
@@ -369,5 +404,9 @@ def test_tile_table_of_the_gpu_kernel_tests_is_the_geometry_of_the_source():
         assert K.TILE1[("fwd", dtype)] == 256 * e and K.TILE1[("inv", dtype)] == 128 * e
         for flen in K.FUSED:
             assert K.tile2("fwd", dtype, flen) == (8, 16 * e) and K.tile2("inv", dtype, flen) == (16, (16 if flen <= 12 else 8) * e)
-    assert "g((unsigned)(blocks < 8192 ? blocks : 8192)), blk(256)" in src and K.GENERIC_GRID == 8192 * 256
-    assert K.FUSED == list(range(2, 21, 2)) and all("MIFWT_BWT_CASE(%d)" % flen in src for flen in K.FUSED)
+    # (the axis launcher is shared and takes the family's grid cap: at most `grid_cap` workgroups of 256)
+    assert "g((unsigned)(blocks < grid_cap ? blocks : grid_cap)), blk(256)" in shared
+    assert "launch_axis(dtype, inverse, total, 8192, stream, a, bwt_axis_generic<" in src and K.GENERIC_GRID == 8192 * 256
+    # (one length dispatch for every fused-level unit: the even lengths 2 .. 20 and no other)
+    assert K.FUSED == list(range(2, 21, 2)) and re.findall(r"MIFWT_LEN_CASE\((\d+)\)\n", shared) == [str(flen) for flen in K.FUSED]
+    assert "for_even_len(d->filt_len," in src and "launch_fused<T, decltype(len)::value>" in src

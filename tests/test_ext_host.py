@@ -326,3 +326,26 @@ def test_ext_supported_answers_on_the_host():
     assert lib.mifwt_ext_fwd(ctypes.byref(d), 0, p, p, det, taps, taps, None) == -2
     assert lib.mifwt_ext_adj(ctypes.byref(d), 0, p, det, p, taps, taps, None) == -2
     assert [_engine.launch_count(k) for k in (42, 43)] == before
+    # a null descriptor, then a null data or tap pointer on a served descriptor: each is refused before any launch
+    assert (lib.mifwt_ext_supported(None, 0, 0), lib.mifwt_ext_kernel_id(None, 0, 1)) == (-1, -1)
+    assert lib.mifwt_ext_fwd(None, 0, p, p, det, taps, taps, None) == -1
+    assert lib.mifwt_ext_adj(None, 0, p, det, p, taps, taps, None) == -1
+    ok = _desc(torch.float32, 8, [4, 4])
+    null_det = (ctypes.c_void_p * 3)(p, None, p)
+    for args in ((None, p, det, taps, taps), (p, None, det, taps, taps), (p, p, None, taps, taps), (p, p, null_det, taps, taps),
+                 (p, p, det, None, taps), (p, p, det, taps, None)):
+        assert lib.mifwt_ext_fwd(ctypes.byref(ok), 0, *args, None) == -1, args
+    for args in ((None, det, p, taps, taps), (p, None, p, taps, taps), (p, null_det, p, taps, taps), (p, det, None, taps, taps),
+                 (p, det, p, None, taps), (p, det, p, taps, None)):
+        assert lib.mifwt_ext_adj(ctypes.byref(ok), 0, *args, None) == -1, args
+    assert [_engine.launch_count(k) for k in (42, 43)] == before
+    # the axis entries: a null data, stride or tap pointer (-1); float16 with valid pointers is outside their envelope (-2, nothing launched)
+    st = (ctypes.c_int64 * 3)(8, 1, 1)
+    before = [_engine.launch_count(k) for k in (44, 45)]
+    for entry in (lib.mifwt_ext_axis_fwd, lib.mifwt_ext_axis_adj):
+        good = [p, st, p, st, p, st, taps, taps]
+        for hole in range(len(good)):
+            assert entry(0, 0, 8, 1, 8, 1, *[None if i == hole else v for i, v in enumerate(good)], None) == -1, hole
+        assert entry(0, 2, 8, 1, 8, 1, *good, None) == -2
+        assert entry(3, 0, 8, 1, 8, 1, *good, None) == -1
+    assert [_engine.launch_count(k) for k in (44, 45)] == before

@@ -43,10 +43,11 @@ The audit (read before the first run: every product that forms an offset or a gr
   15   same file: ``row * approx_rs`` / ``y_rs`` / ``det_rs``.
   17   csrc/mifwt_dwt1_long.hip: ``(int64_t)row * x_rs`` etc.; rows <= 2^24, ``rows * (nchunks + 1) <= 2^30`` (long_plan).
   18   same file: ``(int64_t)row * approx_rs`` / ``y_rs`` / ``det_rs``; ``rows * nchunks <= 2^30`` (inv_long_plan).
-  38/39 csrc/mifwt_per.hip: ``(int64_t)b * sig_bs``, ``(int64_t)gr * sig_rs``, ``(int64_t)b * a_bs + (int64_t)m * a_rs``;
-       ``grid <= INT32_MAX`` (launch_fused), ``tiles <= INT32_MAX`` (fused_check).
-  42/43 csrc/mifwt_ext.hip: the same forms (lines 288, 331-332, 394-395, 410, 422), ``grid <= INT32_MAX``.
-  46/47 csrc/mifwt_cplx.hip: the same forms in complex elements (lines 174, 224-225, 316-317, 326, 343), ``grid <= INT32_MAX``.
+  38/39 csrc/mifwt_per.hip: ``(int64_t)b * sig_bs``, ``(int64_t)gr * sig_rs``; the band offsets ``(int64_t)b * a_bs + (int64_t)m * a_rs``
+       in ``store_bands``, ``grid <= INT32_MAX`` in ``cut_tiles`` and ``tiles <= INT32_MAX`` in ``fused_envelope`` (csrc/mifwt_level_tile.h,
+       shared by 26/27, 38/39, 42/43 and 46/47).
+  42/43 csrc/mifwt_ext.hip: the same forms in the staging and in the adjoint kernels, the same shared pieces.
+  46/47 csrc/mifwt_cplx.hip: the same forms in complex elements in its own kernels; ``cut_tiles`` / ``fused_envelope`` shared.
   48/49 csrc/mifwt_thresh.hip: rows through ``i0 * xs0 + i1 * xs1`` with int64 ``i0``, ``i1``; columns int64; units, rows < 2^31 and
        ``n <= 2^30`` (seg_geometry) — THE DEFECT: ``thresholding._collapse`` merged a dense tensor into one row, so any dense tensor of
        more than 2^30 elements raised ``libmifwt: valid request this build has no kernel for``.  Fixed in ``_collapse`` (the row is cut back
@@ -62,11 +63,12 @@ The audit (read before the first run: every product that forms an offset or a gr
        ``i0 * in0_s[0]`` with int64 strides, ``nrows <= INT32_MAX / 2``, ``n <= INT32_MAX / 4``, ``nblk <= INT32_MAX``.
   40/41 csrc/mifwt_per.hip, per_axis_kernel: ``int64_t idx`` grid-stride loop over ``outer * len * inner`` (int64), ``o * sig_s[0]``,
        ``(int64_t)pos * lo_s[1]``, ``in * sig_s[2]`` with int64 strides; ``n <= INT32_MAX / 4`` (per_axis), at most 65536 blocks.
-  44/45 csrc/mifwt_ext.hip, ext_axis_kernel (lines 463-469): the same loop and products; ``n <= INT32_MAX / 4`` (line 626).
+  44/45 csrc/mifwt_ext.hip, ext_axis_kernel: the same loop and products; ``n <= INT32_MAX / 4`` (``fill_axis_args``, mifwt_level_tile.h,
+       for 28/29, 40/41 and 44/45).
   26/27 csrc/mifwt_bwt.hip: ``(int64_t)b * sig_bs``, ``(int64_t)gr * sig_rs``, ``(int64_t)b * a_bs + (int64_t)m * a_rs``;
-       ``coef_extent <= 2^29``, ``tiles <= INT32_MAX`` (lines 383-386), ``grid <= INT32_MAX`` (line 438).
-  28/29 same file, bwt_axis_generic (lines 309-358): ``int64_t idx`` over ``outer * len * inner``, ``(int64_t)j * sig_s[1]``, table rows
-       ``(int64_t)r * L + k``; ``n <= INT32_MAX / 4`` (line 503), at most 8192 blocks.
+       ``coef_extent <= 2^29``, ``tiles <= INT32_MAX`` (``fused_envelope``), ``grid <= INT32_MAX`` (``cut_tiles``).
+  28/29 same file, bwt_axis_generic: ``int64_t idx`` over ``outer * len * inner``, ``(int64_t)j * sig_s[1]``, table rows
+       ``(int64_t)r * L + k``; ``n <= INT32_MAX / 4`` (``fill_axis_args``), at most 8192 blocks.
   30/31 csrc/mifwt_bwt3.hip: ``(int64_t)b * sig_bs``, ``(int64_t)md * a_ds + (int64_t)mr * a_rs`` (lines 152, 232-233, 269-270, 329);
        ``coef_extent <= 2^29``, ``tiles <= INT32_MAX``, ``grid <= INT32_MAX`` (lines 365-367, 414).
   32/33 csrc/mifwt_bwt_tree.hip: ``const int64_t row = blockIdx.x``, ``row * in_rs``, ``row * n`` (lines 74-79, 124-129);

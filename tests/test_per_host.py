@@ -266,3 +266,26 @@ def test_per_supported_answers_on_the_host():
     assert lib.mifwt_per_fwd(ctypes.byref(d), p, p, det, taps, taps, None) == -2
     assert lib.mifwt_per_inv(ctypes.byref(d), p, det, p, taps, taps, None) == -2
     assert [_engine.launch_count(k) for k in (38, 39)] == before
+    # a null descriptor, then a null data or tap pointer on a served descriptor: each is refused before any launch
+    assert (lib.mifwt_per_supported(None, 0), lib.mifwt_per_kernel_id(None, 1)) == (-1, -1)
+    assert lib.mifwt_per_fwd(None, p, p, det, taps, taps, None) == -1
+    assert lib.mifwt_per_inv(None, p, det, p, taps, taps, None) == -1
+    ok = _desc(torch.float32, 8, [4, 4])
+    null_det = (ctypes.c_void_p * 3)(p, None, p)
+    for args in ((None, p, det, taps, taps), (p, None, det, taps, taps), (p, p, None, taps, taps), (p, p, null_det, taps, taps),
+                 (p, p, det, None, taps), (p, p, det, taps, None)):
+        assert lib.mifwt_per_fwd(ctypes.byref(ok), *args, None) == -1, args
+    for args in ((None, det, p, taps, taps), (p, None, p, taps, taps), (p, null_det, p, taps, taps), (p, det, None, taps, taps),
+                 (p, det, p, None, taps), (p, det, p, taps, None)):
+        assert lib.mifwt_per_inv(ctypes.byref(ok), *args, None) == -1, args
+    assert [_engine.launch_count(k) for k in (38, 39)] == before
+    # the axis entries: a null data, stride or tap pointer (-1); float16 with valid pointers is outside their envelope (-2, nothing launched)
+    st = (ctypes.c_int64 * 3)(8, 1, 1)
+    before = [_engine.launch_count(k) for k in (40, 41)]
+    for entry in (lib.mifwt_per_axis_fwd, lib.mifwt_per_axis_inv):
+        good = [p, st, p, st, p, st, taps, taps]
+        for hole in range(len(good)):
+            assert entry(0, 8, 1, 8, 1, *[None if i == hole else v for i, v in enumerate(good)], None) == -1, hole
+        assert entry(2, 8, 1, 8, 1, *good, None) == -2
+        assert entry(0, 7, 1, 8, 1, *good, None) == -1
+    assert [_engine.launch_count(k) for k in (40, 41)] == before
