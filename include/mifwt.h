@@ -741,6 +741,39 @@ int mifwt_compact_encode(int dtype, const mifwt_estim_band* segs, int nseg, int6
 int mifwt_compact_move(int dtype, int gather, void* const* tensors, const int64_t* sizes, int nseg, int64_t images, int64_t capacity,
                        void* values, const int32_t* indices, const int32_t* counts, void* stream);
 
+/* PACKING — a coefficient container as ONE tensor and back (csrc/mifwt_pack.hip): the copies behind coeffs_to_array / ravel_coeffs and the
+ * copy=True forms of array_to_coeffs / unravel_coeffs.  Nothing is computed: `elem_bytes` (2, 4, 8 or 16) is the element size, which is
+ * all the kernels know of the dtype.  A BOX is a block of four extents, three outer ones and a row, somewhere in the destination:
+ *   dst, dst_stride   its first destination element and the element strides of the three outer extents; destination rows are dense
+ *   src, src_stride   its first source element and the element strides of all four extents (any: a band is read as the strided view it
+ *                     is); src = NULL: the box is filled with the padding element (mifwt_pack_to_array only)
+ *   extent            fewer than 2^31 elements per row, fewer than 2^31 rows per box, fewer than 2^31 units per call
+ * The caller's boxes must tile what it wants written: every destination element of a box is written once, every source element of a
+ * box read once, nothing outside a box is touched.  All offsets are 64-bit.
+ *   mifwt_pack_to_array  (59) up to mifwt_pack_max_boxes() boxes in one launch, fills included; `padding`: elem_bytes bytes on the HOST
+ *   mifwt_pack_to_bands  (60) the same table run the other way (the array is the source, dense bands the destinations); no fills
+ *   mifwt_pack_plan      (host only) the number of units (workgroup iterations) of the call
+ *   mifwt_pack_max_tensors  how many tensors of a container the host layer puts into one launch (24, as mifwt_thresh_max_segments);
+ *                        mifwt_pack_max_boxes() (40) is what those and the fills between them need in 3-D
+ * Nothing is copied to the host and nothing synchronises: the calls can be captured.  MIFWT_ERR_BADARG for another element size, nbox
+ * outside [1, mifwt_pack_max_boxes()], a negative extent, a NULL or misaligned pointer of a non-empty box; MIFWT_ERR_UNSUPPORTED
+ * beyond the index range.  Nothing is launched then, nor for a call whose boxes are all empty.  Counted under their ids by
+ * mifwt_launch_count. */
+#define MIFWT_KID_PACK_TO_ARRAY 59 /* the bands of a container and the padding between them into one dense array, one launch */
+#define MIFWT_KID_PACK_TO_BANDS 60 /* blocks of one array into dense tensors, one launch */
+typedef struct mifwt_pack_box {
+  const void* src;
+  void* dst;
+  int64_t extent[4];
+  int64_t src_stride[4];
+  int64_t dst_stride[3];
+} mifwt_pack_box;
+int mifwt_pack_max_boxes(void);
+int mifwt_pack_max_tensors(void);
+int64_t mifwt_pack_plan(int elem_bytes, const mifwt_pack_box* boxes, int nbox);
+int mifwt_pack_to_array(int elem_bytes, const mifwt_pack_box* boxes, int nbox, const void* padding, void* stream);
+int mifwt_pack_to_bands(int elem_bytes, const mifwt_pack_box* boxes, int nbox, void* stream);
+
 /* Reduction behind the gradients w.r.t. the FILTER TAPS (learnable wavelets: src/ptwt/wavelets_learnable.py; the reference
  * gets them from ATen's conv backward because its taps stay in the autograd graph, src/ptwt/_util.py:132):
  *     out[t] += sum_{row < rows} sum_{k < m_len} a[row, k] * b_ext[row, 2k + c0 + sgn * t],     t in [0, filt_len)
@@ -814,7 +847,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          answered by mifwt_select_route)
  *   56 / 57  the k kept elements of a container per leading index as (values, ascending flat indices): the values in LDS / streaming
  *          count, scan and write (mifwt_compact_encode; answered by mifwt_compact_route)
- *   58     scatter / gather between compacted (values, indices) and dense per-tensor storage (mifwt_compact_move) */
+ *   58     scatter / gather between compacted (values, indices) and dense per-tensor storage (mifwt_compact_move)
+ *   59 / 60  the tensors of a container and the padding between them into one dense array / blocks of one array into dense tensors,
+ *          a box table per launch (mifwt_pack_to_array / mifwt_pack_to_bands; never returned by mifwt_kernel_id) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

@@ -15,7 +15,9 @@ a gradient is wanted).  ``swt*``, the packet trees and the ``Matrix*`` classes t
 HIP launch (``thresholding.py``); ``estimate_sigma`` / ``estimate_thresholds`` / ``shrink`` produce the noise level and the VisuShrink /
 BayesShrink thresholds on the device and apply them (``estimators.py``); ``keep_threshold`` / ``sparsify`` find the k-th largest magnitude
 of every image over a whole container — an exact radix selection on the device — and keep the ``k`` largest coefficients (``sparsify.py``);
-``sparse_encode`` / ``sparse_decode`` compact those ``k`` survivors into ``(values, indices)`` per image and back (``sparse.py``).
+``sparse_encode`` / ``sparse_decode`` compact those ``k`` survivors into ``(values, indices)`` per image and back (``sparse.py``);
+``coeffs_to_array`` / ``array_to_coeffs`` / ``ravel_coeffs`` / ``unravel_coeffs`` turn a container into ONE tensor in PyWavelets' layouts and
+back, one HIP launch each, and ``wavedecn_shapes`` / ``wavedecn_size`` answer for a shape without a transform (``coeff_array.py``).
 
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
@@ -46,6 +48,7 @@ from .thresholding import threshold, threshold_firm
 from .estimators import estimate_sigma, estimate_thresholds, shrink
 from .sparsify import keep_threshold, sparsify
 from .sparse import SparseCoeffs, sparse_decode, sparse_encode
+from .coeff_array import array_to_coeffs, coeffs_to_array, ravel_coeffs, unravel_coeffs, wavedecn_shapes, wavedecn_size
 
 __version__ = "0.1.0"
 
@@ -96,4 +99,10 @@ __all__ = [
     "SparseCoeffs",
     "sparse_encode",
     "sparse_decode",
+    "coeffs_to_array",
+    "array_to_coeffs",
+    "ravel_coeffs",
+    "unravel_coeffs",
+    "wavedecn_shapes",
+    "wavedecn_size",
 ]

@@ -200,6 +200,22 @@ COMPACT_ENTRIES: dict = {
     "mifwt_compact_move": (_c, [_c, _c, _vpp, _i64_p, _c, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
+class PackBox(ctypes.Structure):
+    """``mifwt_pack_box``."""
+
+    _fields_ = [("src", _vp), ("dst", _vp), ("extent", _i64 * 4), ("src_stride", _i64 * 4), ("dst_stride", _i64 * 3)]
+
+
+# The container <-> array copies (coeff_array.py; include/mifwt.h, mifwt_pack_*): bound privately for the same reason.
+_box_p = ctypes.POINTER(PackBox)
+PACK_ENTRIES: dict = {
+    "mifwt_pack_max_boxes": (_c, []),
+    "mifwt_pack_max_tensors": (_c, []),
+    "mifwt_pack_plan": (_i64, [_c, _box_p, _c]),
+    "mifwt_pack_to_array": (_c, [_c, _box_p, _c, _vp, _vp]),
+    "mifwt_pack_to_bands": (_c, [_c, _box_p, _c, _vp]),
+}
+
 _MAY_BE_MISSING = {"mifwt_workspace_bytes_dtaps", "mifwt_kernel_id_dtaps", "mifwt_dwt_fwd_dtaps", "mifwt_dwt_inv_dtaps", "mifwt_dwt_fwd_adjoint_dtaps",
                    "mifwt_dwt_inv_adjoint_dtaps", "mifwt_launch_count", "mifwt_tap_correlate_planes", "mifwt_dwt1_inv_outer", "mifwt_dwt1_fwd_outer"}
 _abi_mismatch = False

@@ -984,14 +984,24 @@ def _walk_synthesis(shape: Tuple[int, ...], folded, flen: int, ndim: int, separa
 
 def _pyramid_route(cur: torch.Tensor, folded, exts, flen: int, separable: bool):
     """Which levels of a 2-D float32 reconstruction go in ONE launch, the running approximation kept on chip (mifwt_dwt2_inv_pyramid):
-    ``(first level of that launch, its plan)`` — every level of a small plane, the FINEST up to three of a big one (that is where the
-    bytes are; what is coarser goes first, level by level) — or ``(number of levels, None)``.  Geometry only; ``exts`` from the walk."""
+    ``(first level of that launch, its plan, whether strided planes are copied first)`` — every level of a small plane, the FINEST up to three of a big one (that is where the
+    bytes are; what is coarser goes first, level by level) — or ``(number of levels, None, False)``.  Geometry only; ``exts`` from the walk."""
     eng, nlev = _engine.ENGINE, len(folded)
     if cur.dtype != torch.float32:
-        return nlev, None
+        return nlev, None, False
     if folded[-1][0].shape[-1] * folded[-1][0].shape[-2] <= 10240:  # (the finest level's four coefficient planes must fit into LDS)
         pl = eng.synthesis_pyramid_plan(cur, folded, flen, exts[-1])
-        return (0, pl) if pl is not None and pl[3] else (nlev, None)
+        if pl is not None and pl[3]:
+            return 0, pl, False
+        # the one-launch kernel reads dense planes.  Planes with a row pitch of their own — views of a larger array, as
+        # array_to_coeffs hands out — are copied first (they are small) and take the same launch, so the result of a reconstruction
+        # does not depend on where its coefficients lie: the per-level kernels sum in another order.  The third entry says "copy".
+        if not separable:
+            meta = lambda t: torch.empty(t.shape, dtype=t.dtype, device="meta")
+            pl = eng.synthesis_pyramid_plan(meta(cur), [[meta(t) for t in lv] for lv in folded], flen, exts[-1])
+            if pl is not None and pl[3] == 1:
+                return 0, pl, True
+        return nlev, None, False
     for first in range(max(nlev - 3, 0), nlev):
         if first == 0:
             a0 = cur[tuple(slice(0, s_) for s_ in folded[0][0].shape)] if separable else cur
@@ -1002,8 +1012,8 @@ def _pyramid_route(cur: torch.Tensor, folded, exts, flen: int, separable: bool):
             a0 = torch.empty(ext, dtype=cur.dtype, device="meta")
         pl = eng.synthesis_pyramid_plan(a0, folded[first:], flen, exts[-1])
         if pl is not None and pl[3] == 2:
-            return first, pl
-    return nlev, None
+            return first, pl, False
+    return nlev, None, False
 
 
 def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, axes: AxisHint, ndim: int,
@@ -1050,14 +1060,14 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
         hit = _rec_memo.get(gkey)
     if hit is None:
         exts, err = _walk_synthesis(tuple(cur.shape), folded, flen, ndim, separable)
-        hit = (exts, nlev, None)
+        hit = (exts, nlev, None, False)
         if gkey is not None and err is None:  # (the fused routes are considered only when the whole walk passes)
             if ndim == 2:
                 hit = (exts, *_pyramid_route(cur, folded, exts, flen, separable))
             if len(_rec_memo) > 1024:
                 _rec_memo.clear()
             _rec_memo[gkey] = hit
-    exts, upto, plan = hit
+    exts, upto, plan, densify = hit  # (densify: small planes with a row pitch get dense copies for the one-launch kernel, _pyramid_route)
     stop = -1 if err is None else len(exts)  # the level at which the loop below raises the reference's error
     pos = 0
     if ndim == 1 and not separable and nlev >= 2 and fusable and stop < 0:
@@ -1106,6 +1116,9 @@ def synthesis(approx: torch.Tensor, levels: List[List[torch.Tensor]], wavelet, a
         if pos == upto:
             # the rest in one launch (the plan was made for a dense hand-over approximation; a strided one — a separable crop — is
             # looked up afresh)
+            if densify:  # (one launch of kernel 60 for all planes was tried and is slower, host-bound: EXPERIMENTS part M)
+                cur = cur.contiguous()
+                folded = folded[:pos] + [[t.contiguous() for t in lv] for lv in folded[pos:]]
             same = pos == 0 or cur.is_contiguous()
             if any_grad:
                 y = _SynthesisPyramid.apply(rec_lo, rec_hi, tuple(exts[-1]), plan if same else None, nlev - pos, cur,
