@@ -20,9 +20,10 @@ only and the sums of squares are added in a fixed order in float64: two runs giv
 
 Two routes select.  An image of at most :func:`lds_capacity` elements is selected by one workgroup from keys held in LDS (id 50); a
 longer one by digit passes over the band with per-workgroup LDS histograms flushed into integer counters (id 51).  ``FORCE_STREAM``
-sends every size down the second route (tests, tools).  Limits: fewer than 2^31 elements per leading index, and the collapsed form of
-``thresholding._form``; beyond them the call is composed from torch operations (:func:`_composed_sigma`, :func:`_composed_moment`).
-float32 and float64 data only.
+sends every size down the second route (tests, tools).  Limits: the collapsed form of ``thresholding._form``, beyond which the call is
+composed from torch operations (:func:`_composed_sigma`, :func:`_composed_moment`), and fewer than 2^31 elements per leading index:
+from there on the moments are composed and the order statistics raise ``ValueError`` (their composition is ``torch.sort``, which takes
+at most 2^31 - 1 elements along the sorted axis).  float32 and float64 data only.
 """
 from __future__ import annotations
 
@@ -152,6 +153,15 @@ def _composed_sigma(d: torch.Tensor, lead: int):
     return stats, sigma
 
 
+def _check_count(d: torch.Tensor, lead: int) -> None:
+    """The order statistics of 2^31 elements per leading index and more are refused: no kernel takes them, and neither does the sort
+    of the composition."""
+    images = math.prod(d.shape[:lead])
+    count = d.numel() // images if images else 0
+    if count >= _COUNT_LIMIT:
+        raise ValueError(f"estimate_sigma: the order statistics take fewer than 2^31 elements per leading index, got {count}")
+
+
 def _select(d: torch.Tensor, lead: int, want_stats: bool = False):
     """(sigma in ``d``'s dtype [images], the same values in float64 [images], the two order statistics [images, 2] or None) of a
     non-empty band ``d`` on the device."""
@@ -181,12 +191,14 @@ def _select(d: torch.Tensor, lead: int, want_stats: bool = False):
 def _order_stats(d: torch.Tensor, lead: int = 0) -> torch.Tensor:
     """The order statistics of ``|d|`` of rank ``(c - 1) // 2`` and ``c // 2`` per leading index, shape ``d.shape[:lead] + (2,)`` (tests)."""
     _check_dtype(d)
+    _check_count(d, lead)
     _engine._require_gpu(d)
     return _select(d, lead, want_stats=True)[2].reshape(tuple(d.shape[:lead]) + (2,))
 
 
 def _sigma_of(d: torch.Tensor, lead: int):
     """(sigma [lead shape], sigma as float64 [images]) of the band ``d``; NaN for an empty band (numpy's median of nothing), no launch."""
+    _check_count(d, lead)
     _engine._require_gpu(d)
     shape = tuple(d.shape[:lead])
     images = math.prod(shape)
@@ -205,7 +217,8 @@ def estimate_sigma(data, *, lead: Optional[int] = None) -> torch.Tensor:
 
     The median is numpy's (even counts: the mean of the two middle order statistics, which are exact; mean and division in float64,
     rounded once).  Zeros are not masked out, unlike scikit-image.  A zero-size leading axis gives an empty result, an empty band NaN,
-    both without a launch.  ``ValueError`` for complex, 16-bit, integer or bool data; ``RuntimeError`` for a CPU tensor."""
+    both without a launch.  ``ValueError`` for complex, 16-bit, integer or bool data and for 2^31 elements per leading index or more;
+    ``RuntimeError`` for a CPU tensor."""
     d, lead = _finest(data, lead)
     return _sigma_of(d, lead)[0]
 

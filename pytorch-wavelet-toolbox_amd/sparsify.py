@@ -21,8 +21,9 @@ Integer counters only: two runs give the same bits.
 Two routes select.  A pool of at most ``estimators.lds_capacity`` elements per image in at most :func:`max_segments` tensors is selected
 by one workgroup from keys held in LDS (id 54); anything else by digit passes over all tensors with per-workgroup LDS histograms flushed
 into integer counters (id 55), ``max_segments`` tensors per launch.  ``FORCE_STREAM`` sends every size down the second route (tests,
-tools).  Limits: fewer than 2^31 pooled elements per image, and the collapsed form of ``thresholding._form``; beyond them the value is
-composed from torch operations (:func:`_composed_kth`).  float32 and float64 data only.
+tools).  Limits: the collapsed form of ``thresholding._form``, beyond which the value is composed from torch operations
+(:func:`_composed_kth`), and fewer than 2^31 pooled elements per image: ``ValueError`` from there on (the composition is ``torch.sort``,
+which takes at most 2^31 - 1 elements along the sorted axis).  float32 and float64 data only.
 
 The package exports the FUNCTION under this module's name, so ``ptwt_amd.sparsify`` is :func:`sparsify`; the module and its switches
 are reached with ``importlib.import_module("ptwt_amd.sparsify")``.
@@ -144,7 +145,7 @@ def _kth(tensors: Sequence[torch.Tensor], lead: int, shape: Tuple[int, ...], n: 
         v = torch.full(shape, float("inf"), dtype=t0.dtype, device=t0.device)
         return v, v.reshape(-1).double()
     live = [t.detach() for t in tensors if t.numel()]
-    bands = [_est._band(t, lead) for t in live] if n < _COUNT_LIMIT else [None]
+    bands = [_est._band(t, lead) for t in live]
     cell = (t0.dtype, n)
     if any(b is None for b in bands) or cell in COMPOSED_CELLS:
         v = _composed_kth(live, lead, k, dk)
@@ -167,6 +168,8 @@ def _kth(tensors: Sequence[torch.Tensor], lead: int, shape: Tuple[int, ...], n: 
 
 def _value(coeffs, keep, approx: bool, lead: Optional[int]):
     leaves, pooled, lead, shape, n = _pool(coeffs, approx, lead)
+    if n >= _COUNT_LIMIT:  # no kernel takes such a pool, and neither does the sort of the composition
+        raise ValueError(f"sparsify: the selection takes fewer than 2^31 pooled coefficients per image, got {n}")
     k, dk = _keep(keep, n, shape, leaves[0].device)
     for t in leaves:
         _engine._require_gpu(t)
@@ -185,7 +188,7 @@ def keep_threshold(coeffs, keep, *, approx: bool = False, lead: Optional[int] = 
 
     ``k = 0`` gives ``+inf``; so does an empty pool, without a launch; a zero-size leading axis gives an empty result without a launch.
     NaN inputs are unspecified.  ``ValueError`` for complex, 16-bit, integer or bool data, for tensors that do not share dtype, device and
-    leading shape, and for any other ``keep``; ``RuntimeError`` for a CPU tensor."""
+    leading shape, for any other ``keep`` and for a pool of 2^31 or more elements per image; ``RuntimeError`` for a CPU tensor."""
     return _value(coeffs, keep, approx, lead)[2]
 
 

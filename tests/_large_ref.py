@@ -1,6 +1,7 @@
 """Helpers of tests/test_gpu_large_offsets.py: which items of a batch to compare with the float64 reference when the batch's buffers
 cross 2^31 / 2^32 bytes or elements, how to cut the batch into slices of a size the other modules already pin, and the per-item
-norm-wise error of two results on the device.  No GPU is needed for the first two (tests/test_large_ref_host.py).
+norm-wise error of two results on the device; and, for tests/test_gpu_large_offsets_post.py, the counting check of an order statistic
+of a pool too large to sort.  No GPU is needed for any but the error norm (tests/test_large_ref_host.py).
 
 A BUFFER is described by ``(item stride in elements, element size in bytes)``: item ``i`` of the batch starts ``i * stride`` elements
 behind the buffer's base (a band that is a plane of a level buffer [B, 4, M, M] has the stride of that buffer, 4 M M)."""
@@ -252,6 +253,70 @@ def window_reference(fam, analysis, gather, in_extent, out_extent, start, size=W
     crops = gather(idxs)
     outs = fam.fwd(crops) if analysis else fam.inv(crops, ext)
     return [t[(Ellipsis, *win)] for t in outs]
+
+
+# ---- order statistics of a pool too large to sort: the counting check -----------------------------------------------------------------
+# v is the k-th largest magnitude of a pool (s[n - k], s the ascending sort of |x|) if and only if v occurs among the |x| and
+# count(|x| > v) < k <= count(|x| >= v).  The counts are integer sums of comparisons, chunk by chunk on the device of the data; the
+# magnitudes are compared as their bit patterns with the sign cleared (for non-negative IEEE numbers integer order is value order, and
+# -0.0, denormals and inf need no floating-point mode).  Nothing is sorted, selected or histogrammed.
+COUNT_CHUNK = 1 << 27
+_KEY = {torch.float32: (torch.int32, (1 << 31) - 1), torch.float64: (torch.int64, (1 << 63) - 1)}
+
+
+def magnitude_keys(t):
+    """The bit patterns of ``t`` (float32 / float64, any strides) with the sign cleared, as signed integers of the same width."""
+    itype, mask = _KEY[t.dtype]
+    return t.view(itype) & mask
+
+
+def _chunks(t, limit):
+    """Views of ``t`` of at most ``limit`` elements each (one row of the first axis where a row is longer) that cover it once."""
+    if t.dim() == 0:
+        t = t.reshape(1)
+    if t.is_contiguous():
+        t = t.reshape(-1)
+    per = max(1, limit // max(1, t[0].numel())) if t.shape[0] else 1
+    for s in range(0, t.shape[0], per):
+        part = t[s:s + per]
+        if part.numel() > limit and part.dim() > 1:
+            for q in part.unbind(0):
+                yield from _chunks(q, limit)
+        else:
+            yield part
+
+
+def magnitude_counts(tensors, v, chunk=COUNT_CHUNK):
+    """``(count(|x| > v), count(|x| == v))`` over every element of the tensors ``tensors`` (one dtype, one device) as Python ints;
+    ``v``: a number, a numpy scalar or a one-element tensor holding a value of that dtype."""
+    t0 = tensors[0]
+    value = v.detach().reshape(()).to("cpu", t0.dtype) if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=t0.dtype)
+    key = int(magnitude_keys(value))
+    greater = torch.zeros((), dtype=torch.int64, device=t0.device)
+    equal = torch.zeros((), dtype=torch.int64, device=t0.device)
+    for t in tensors:
+        assert t.dtype == t0.dtype
+        for part in _chunks(t, chunk):
+            keys = magnitude_keys(part)
+            greater += (keys > key).sum()
+            equal += (keys == key).sum()
+            del keys
+    return int(greater), int(equal)
+
+
+def is_kth_largest(tensors, v, k, chunk=COUNT_CHUNK):
+    """(whether ``v`` is the k-th largest magnitude of the pool ``tensors``, count(|x| > v), count(|x| == v)); ``k = 0`` asks for
+    ``+inf`` (the k-th largest of nothing), as ``keep_threshold`` defines it."""
+    greater, equal = magnitude_counts(tensors, v, chunk)
+    if k == 0:
+        return float(v) == float("inf"), greater, equal
+    return equal > 0 and greater < k <= greater + equal, greater, equal
+
+
+def median_ranks(count):
+    """``(k_lo, k_hi)``: the two middle order statistics of ``count`` magnitudes — ascending ranks ``(count - 1) // 2`` and
+    ``count // 2``, whose mean is numpy's median (tests/_estimator_ref.py) — as k-th LARGEST: ascending rank r is k = count - r."""
+    return count - (count - 1) // 2, count - count // 2
 
 
 def item_relerr(got, want):

@@ -129,6 +129,60 @@ def test_cabi_answers_without_a_device():
     assert lib.mifwt_estim_moments_plan(0, arr, 0, 3) == -1
 
 
+def _guard_band(ext, rp=0):
+    b = _engine.EstimBand()
+    b.extent[:] = ext
+    b.stride[:] = [ext[1] * ext[2], ext[2], 1]
+    b.rows_per_index = rp
+    return b
+
+
+#: the guards of ``band_geometry`` (csrc/mifwt_bands.h) as the estimator entries answer them: (what, band, rows per image, the answer of
+#: ``mifwt_estim_select_route``) — the last accepted value and the first refused one (-2: MIFWT_ERR_UNSUPPORTED).  No data pointer.
+GUARDS = [
+    ("n = 2^30", [1, 1, 1 << 30], 0, 51), ("n = 2^30 + 1", [1, 1, (1 << 30) + 1], 0, -2),
+    ("e1 = 2^30", [1, 1 << 30, 1], 1, 50), ("e1 = 2^30 + 1", [1, (1 << 30) + 1, 1], 1, -2),
+    ("rows = 2^31 - 1", [(1 << 31) - 1, 1, 1], 1, 50), ("rows = 2^31", [2, 1 << 30, 1], 1, -2), ("rows = 2^31, one axis", [1 << 31, 1, 1], 1, -2),
+    ("rp n = 2^31 - 2", [1, 2, (1 << 30) - 1], 0, 51), ("rp n = 2^31 - 1", [(1 << 31) - 1, 1, 1], 0, 51),
+    ("rp n = 2^31", [1, 2, 1 << 30], 0, -2), ("rp n = 2^31, short rows", [2, 1 << 30, 1], 0, -2),
+]
+
+
+@pytest.mark.parametrize("what,ext,rp,want", GUARDS, ids=[g[0] for g in GUARDS])
+def test_guards_of_the_band_geometry(what, ext, rp, want):
+    lib = E._lib()
+    for dt in (0, 1):
+        got = lib.mifwt_estim_select_route(dt, _guard_band(ext, rp), 0)
+        assert got == (want if want < 0 or dt == 0 or want == 51 else 50), (what, dt, got)
+        ws = lib.mifwt_estim_select_workspace(dt, _guard_band(ext, rp), 51)
+        images = (ext[0] * ext[1]) // (rp if rp else ext[0] * ext[1])
+        assert ws == (0 if want < 0 else images * (2 * 2 * 2048 * 4 + 2 * (16 if dt == 0 else 24))), (what, dt, ws)
+        assert lib.mifwt_estim_sigma(dt, _guard_band(ext, rp), 51, None, None, None, None, 0, None) == (want if want < 0 else -1)  # (no pointer)
+
+
+def test_guards_of_the_moments_plan_and_the_python_limits():
+    """Units of a moments launch: fewer than 2^31 over all segments; images below 2^31; and the limits the Python side decides with
+    are the library's — ``_COUNT_LIMIT`` the first refused count per image, ``thresholding.ROW_LIMIT`` the last accepted row."""
+    lib = E._lib()
+    plan = lambda images, k: lib.mifwt_estim_moments_plan(0, (_engine.EstimBand * k)(*[_guard_band([images, 1, 1], 1)] * k), k, images)
+    assert plan((1 << 30) - 1, 2) == (1 << 31) - 2 and plan(1 << 30, 2) == -2  # one unit per image and segment
+    assert plan((1 << 31) - 1, 1) == (1 << 31) - 1 and plan(1 << 31, 1) == -1  # images
+    assert lib.mifwt_estim_thresholds(0, 0, None, 1, 1 << 31, None, 1.0, None, None, None, None, 0, None) == -1
+    one = lambda count: lib.mifwt_estim_select_route(0, _guard_band([1, 2, count // 2]), 0)
+    assert E._COUNT_LIMIT == 1 << 31 and one(E._COUNT_LIMIT - 2) == 51 and one(E._COUNT_LIMIT) == -2
+    from ptwt_amd import thresholding as T
+    row = lambda n: lib.mifwt_estim_select_route(0, _guard_band([1, 1, n]), 0)
+    assert T.ROW_LIMIT == 1 << 30 and row(T.ROW_LIMIT) == 51 and row(T.ROW_LIMIT + 1) == -2
+    assert T._ROWS_LIMIT == 1 << 31
+    # what the Python side hands over just inside and past the limit: a row of 2^30 + 4096 is cut into two, 46340^2 into two rows,
+    # 46341^2 (2^31 + 4633 elements) has a form of three rows but no kernel: ``_band`` answers None and the call is composed or refused
+    meta = lambda *shape: torch.empty(shape, device="meta")
+    assert E._band(meta(1, (1 << 30) + 4096), 0)[1:] == ((1, 2, (1 << 29) + 2048), (0, (1 << 29) + 2048, 1), 0, (1 << 30) + 4096)
+    assert E._band(meta(1, (1 << 30) + 4096), 1)[1:] == ((1, 2, (1 << 29) + 2048), (0, (1 << 29) + 2048, 1), 2, (1 << 30) + 4096)
+    assert E._band(meta(46340, 46340), 0)[1:] == ((1, 2, 46340 * 23170), (0, 46340 * 23170, 1), 0, 46340 * 46340)
+    assert E._band(meta(46341, 46341), 0) is None and 46341 * 46341 >= E._COUNT_LIMIT > 46340 * 46340
+
+
 # ---- errors, before any launch ----------------------------------------------------------------------------------------------------------
 def _coeffs(dtype=torch.float32):
     return [torch.zeros(2, 3, 3, dtype=dtype), WaveletDetailTuple2d(*[torch.ones(2, 3, 3, dtype=dtype) for _ in range(3)])]
@@ -187,3 +241,16 @@ def test_unknown_method_mode_and_bad_arguments():
     ragged[0] = torch.zeros(3, 3, 3)
     with pytest.raises(ValueError, match="leading shape"):
         ptwt_amd.estimate_thresholds(ragged)
+
+
+def test_2_to_the_31_elements_per_image_are_refused_before_a_device_is_needed():
+    """Past ``_COUNT_LIMIT`` no kernel takes the image and ``torch.sort``, the composition's selection, takes at most 2^31 - 1 elements:
+    a ``ValueError`` that names the limit (meta tensors: nothing is allocated)."""
+    past, inside = torch.empty((46341, 46341), device="meta"), torch.empty((46340, 46340), device="meta")
+    for fn in (ptwt_amd.estimate_sigma, E._order_stats):
+        with pytest.raises(ValueError, match=r"fewer than 2\^31 elements per leading index, got 2147488281"):
+            fn(past)
+        with pytest.raises(RuntimeError):  # (inside the limit the call goes on to ask for a GPU tensor)
+            fn(inside)
+        with pytest.raises(RuntimeError):
+            fn(past, lead=1)  # 46341 elements per leading index

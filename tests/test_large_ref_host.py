@@ -163,3 +163,68 @@ def test_item_relerr():
     assert err[0] == 0 and err[1] == 0 and err[3] == 0 and 1e-4 < err[2] < 1e-2 and err[4] > 0.5
     c = torch.randn(2, 6, generator=g, dtype=torch.float64).to(torch.complex64).reshape(2, 6)
     assert L.item_relerr(c, c).tolist() == [0.0, 0.0]
+
+
+# ---- the counting check of tests/test_gpu_large_offsets_post.py -------------------------------------------------------------------------
+def _sorted_magnitudes(arrays):
+    return np.sort(np.concatenate([np.abs(a).reshape(-1) for a in arrays]))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_counting_check_against_a_sort_on_adversarial_pools(dtype):
+    """``is_kth_largest`` says yes to ``numpy.sort(|x|)[n - k]`` and no to every other value, on the pools of tests/_sparsify_ref.py
+    and tests/_estimator_ref.py (ties at the cut, -0.0, denormals, inf, bits that differ in the last digit), in chunks smaller than
+    the pool, over several tensors, one of them a strided view."""
+    from tests import _estimator_ref as RE
+    from tests import _sparsify_ref as RS
+    n = 301
+    pools = {f"sparsify {k}": v[0] for k, v in RS.pools(dtype, 1, n, seed=4).items()}
+    pools.update({f"estimator {k}": v for k, v in RE.adversarial(dtype, n, seed=5).items()})
+    pools["tie free"] = RS.tie_free(dtype, 1, n, seed=6)[0]
+    for name, values in pools.items():
+        wide = torch.from_numpy(np.stack([values[100:], values[100:]], 1).copy())
+        tensors = [torch.from_numpy(values[:100].copy()).reshape(4, 25), wide[:, 0]]  # (the second: stride 2)
+        assert not tensors[1].is_contiguous()
+        s = _sorted_magnitudes([values])
+        distinct = np.unique(s)
+        for k in (1, 2, 3, n // 2, (n + 1) // 2, n - 1, n):
+            v = s[n - k]
+            ok, greater, equal = L.is_kth_largest(tensors, v, k, chunk=64)
+            assert ok and greater == int((s > v).sum()) and equal == int((s == v).sum()), (name, k)
+            assert L.is_kth_largest(tensors, torch.tensor(v), k, chunk=7)[0], (name, k)  # a tensor value, another chunking
+            for other in distinct[distinct != v][:: max(1, distinct.size // 5)]:  # another value of the pool is not the k-th largest
+                assert not L.is_kth_largest(tensors, other, k, chunk=64)[0], (name, k, other)
+            if np.isfinite(v) and v > 0:  # a value between two of the pool has the right counts and does not occur
+                between = np.nextafter(v, dtype(0), dtype=dtype)
+                if between not in distinct:
+                    assert not L.is_kth_largest(tensors, between, k, chunk=64)[0], (name, k)
+        assert L.is_kth_largest(tensors, np.inf, 0)[0]  # k = 0: +inf and nothing else
+        assert s[-1] == np.inf or not L.is_kth_largest(tensors, s[-1], 0)[0]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_counting_check_every_rank_of_a_small_pool(dtype):
+    values = np.array([0.0, -0.0, 1.5, -1.5, 1.5, np.inf, -3.0, 2.0 ** -140 if dtype == np.float32 else 5e-324, 0.25, -0.25, 7.0], dtype=dtype)
+    t = [torch.from_numpy(values)]
+    s = _sorted_magnitudes([values])
+    n = values.size
+    for k in range(1, n + 1):
+        for v in np.unique(s):
+            assert L.is_kth_largest(t, v, k, chunk=3)[0] == bool(v == s[n - k]), (k, v)
+    assert L.magnitude_counts(t, 0.0) == (9, 2) and L.magnitude_counts(t, -0.0) == (9, 2)  # -0.0 is 0.0
+    assert L.magnitude_counts(t, 1.5) == (3, 3) and L.magnitude_counts(t, np.inf) == (0, 1)
+    assert L.magnitude_keys(torch.from_numpy(values)).min() == 0
+
+
+def test_median_through_the_counting_check():
+    """``median_ranks``: the two order statistics whose mean is numpy's median (tests/_estimator_ref.py), odd and even counts."""
+    from tests import _estimator_ref as RE
+    assert L.median_ranks(1) == (1, 1) and L.median_ranks(2) == (2, 1) and L.median_ranks(5) == (3, 3) and L.median_ranks(6) == (4, 3)
+    for count in (1, 2, 7, 64, 301):
+        for name, x in RE.adversarial(np.float32, count, seed=count).items():
+            lo, hi = RE.order_stats(x)
+            k_lo, k_hi = L.median_ranks(count)
+            t = [torch.from_numpy(x)]
+            assert L.is_kth_largest(t, lo, k_lo, chunk=50)[0] and L.is_kth_largest(t, hi, k_hi, chunk=50)[0], (name, count)
+            if np.isfinite(lo) and np.isfinite(hi):
+                assert (np.float64(lo) + np.float64(hi)) * 0.5 / RE.MAD_SCALE == RE.estimate_sigma(x), (name, count)

@@ -467,3 +467,27 @@ def test_cabi_answers_without_a_device():
     assert to_array(4, pad, _box([1, 1, 1, 5], src=2, dst=4)) == -1 and to_bands(8, _box([1, 1, 1, 5], src=8, dst=4)) == -1  # misaligned
     assert to_array(4, pad, _box([1, 0, 1, 5], src=None, dst=None)) == 0 and to_bands(2, _box([0, 1, 1, 5])) == 0  # nothing to write
     assert to_array(5, pad, _box([1, 1, 1, 5])) == -1 and to_bands(4, _box([1, 1, 1, 1 << 31])) == -2
+
+
+#: the guards of ``box_units`` / ``build_args`` (csrc/mifwt_pack.hip) as ``mifwt_pack_plan`` answers them: (what, element size, boxes,
+#: the answer: units, or -2 = MIFWT_ERR_UNSUPPORTED) — the last accepted value and the first refused one
+PACK_GUARDS = [
+    ("row of 2^31 - 1", 2, [[1, 1, 1, (1 << 31) - 1]], None), ("row of 2^31", 2, [[1, 1, 1, 1 << 31]], -2),
+    ("2^31 - 1 rows of 2", 2, [[1, 1, (1 << 31) - 1, 2]], -(-((1 << 31) - 1) // 512)), ("2^31 rows of 2", 2, [[2, 1, 1 << 30, 2]], -2),
+    ("2^31 rows on one axis", 2, [[1, 1, 1 << 31, 2]], -2), ("2^31 + 8 rows of 2", 2, [[(1 << 31) + 8, 1, 1, 2]], -2),
+    ("2^31 - 2 units", 4, [[1, 1, 715827882, 8192]], (1 << 31) - 2), ("2^31 + 1 units", 4, [[1, 1, 715827883, 8192]], -2),
+    ("2^31 - 2 units in two boxes", 4, [[1, 1, 715827881, 8192], [1, 1, 1, 8192]], (1 << 31) - 2),
+    ("2^31 units in two boxes", 4, [[1, 1, 715827882, 8192], [1, 1, 2000, 1]], -2),
+]
+
+
+@pytest.mark.parametrize("what,esz,boxes,want", PACK_GUARDS, ids=[g[0] for g in PACK_GUARDS])
+def test_guards_of_the_pack_plan(what, esz, boxes, want):
+    lib = C._lib()
+    arr = (_engine.PackBox * len(boxes))(*[_box(ext) for ext in boxes])
+    got = lib.mifwt_pack_plan(esz, arr, len(boxes))
+    if want is None:  # one row of 2^31 - 1 float16: slots = (n + 14) / 8, units of about 1024 slots with none empty
+        vpr = ((1 << 31) - 1 + 14) // 8
+        upr = -(-vpr // 1024)
+        want = -(-vpr // -(-vpr // upr))
+    assert got == want, (what, got)

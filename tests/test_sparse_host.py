@@ -234,6 +234,42 @@ def test_cabi_answers_without_a_device():
     assert move([1 << 30, 1 << 30], 1, 1) == -2  # int32 indices
 
 
+def test_guards_of_the_compaction():
+    """The last accepted value and the first refused one of every guard of csrc/mifwt_compact.hip that answers without a device, and
+    ``_INDEX_LIMIT`` against them."""
+    lib = S._lib()
+
+    def arr(bands):
+        return (_engine.EstimBand * len(bands))(*bands), len(bands)
+
+    route = lambda bands, images: lib.mifwt_compact_route(0, *arr(bands), images, 0)
+    ws = lambda bands, images: lib.mifwt_compact_workspace(0, *arr(bands), images, 57)
+    enc = lambda bands, images: lib.mifwt_compact_encode(0, *arr(bands), images, 1, None, 0, 1, 57, None, None, None, None, None, 0, None)
+    # elements per row, pooled elements per image (the int32 flat index), images
+    assert route([_band([1, 1, 1 << 30])], 1) == 57 and route([_band([1, 1, (1 << 30) + 1])], 1) == -2
+    inside = [_band([1, 1, 1 << 30]), _band([1, 1, (1 << 30) - 1])]
+    assert route(inside, 1) == 57 and route(inside + [_band([1, 1, 1])], 1) == -2
+    assert enc(inside, 1) == -1 and enc(inside + [_band([1, 1, 1])], 1) == -2  # (stopped at the missing pointer / refused)
+    assert route([_band([(1 << 31) - 1, 1, 1], 1)], (1 << 31) - 1) == 56 and route([_band([1 << 31, 1, 1], 1)], 1 << 31) == -1
+    assert S._INDEX_LIMIT == 1 << 31 and route([_band([1, 2, (S._INDEX_LIMIT - 2) // 2])], 1) == 57
+    assert route([_band([1, 2, S._INDEX_LIMIT // 2])], 1) == -2
+    # units of one launch (its segments x images, one unit per segment and image here): fewer than 2^31; the workspace of a refused
+    # plan is the quota alone, which ``mifwt_compact_encode`` turns into MIFWT_ERR_UNSUPPORTED
+    seg = lambda images: _band([images, 1, 1], 1)
+    assert ws([seg((1 << 30) - 1)] * 2, (1 << 30) - 1) == (2 * 2 + 1) * ((1 << 30) - 1) * 4
+    assert ws([seg(1 << 30)] * 2, 1 << 30) == (1 << 30) * 4
+    # ... and across the launches of more than 24 segments: every launch has its own grid
+    many = -(-(1 << 31) // 24)
+    assert ws([seg(many - 1)] * 25, many - 1) == (2 * 25 + 1) * (many - 1) * 4 and ws([seg(many)] * 25, many) == many * 4
+    assert ws([seg(many)] * 23, many) == (2 * 23 + 1) * many * 4  # (fewer segments: the same images are inside)
+    # the scatter / gather: int32 indices, the grid
+    move = lambda sizes, images, capacity: lib.mifwt_compact_move(0, 0, (_engine._vp * len(sizes))(), (_engine._i64 * len(sizes))(*sizes),
+                                                                  len(sizes), images, capacity, None, None, None, None)
+    assert move([1 << 30, (1 << 30) - 1], 1, 1) == -1 and move([1 << 30, (1 << 30) - 1, 1], 1, 1) == -2  # (no pointers / refused)
+    assert move([S._INDEX_LIMIT - 1], 1, 1) == -1 and move([S._INDEX_LIMIT], 1, 1) == -2
+    assert move([4], 1 << 31, 1) == -1
+
+
 # ---- errors, before any device is needed ---------------------------------------------------------------------------------------------------
 def _coeffs(dtype=torch.float32):
     return [torch.zeros(2, 3, 3, dtype=dtype), WaveletDetailTuple2d(*[torch.ones(2, 3, 3, dtype=dtype) for _ in range(3)])]  # n = 27

@@ -164,6 +164,36 @@ def test_cabi_answers_without_a_device():
     assert kth([_band([1, 0, 5])], 0, 0, 54) == 0  # nothing to select from
 
 
+#: the guards of ``pool_of`` (csrc/mifwt_bands.h) as ``mifwt_select_route`` answers them: (what, bands as (extents, rows per image),
+#: images, the answer) — the last accepted value and the first refused one (-1: MIFWT_ERR_BADARG, -2: MIFWT_ERR_UNSUPPORTED)
+POOL_GUARDS = [
+    ("n = 2^30", [([1, 1, 1 << 30], 0)], 1, 55), ("n = 2^30 + 1", [([1, 1, (1 << 30) + 1], 0)], 1, -2),
+    ("pooled 2^31 - 1", [([1, 1, 1 << 30], 0), ([1, 1, (1 << 30) - 1], 0)], 1, 55),
+    ("pooled 2^31", [([1, 1, 1 << 30], 0), ([1, 1, (1 << 30) - 1], 0), ([1, 1, 1], 0)], 1, -2),
+    ("pooled 2^31 in 25 segments", [([1, 1, 1 << 27], 0)] * 16 + [([1, 1, 1], 0)] * 9, 1, -2),
+    ("pooled 2^31 - 1 in 25 segments", [([1, 1, 1 << 27], 0)] * 15 + [([1, 1, (1 << 27) - 9], 0)] + [([1, 1, 1], 0)] * 8, 1, 55),
+    ("images 2^31 - 1", [([(1 << 31) - 1, 1, 1], 1)], (1 << 31) - 1, 54), ("images 2^31", [([1 << 31, 1, 1], 1)], 1 << 31, -1),
+    ("rows 2^31", [([2, 1 << 30, 1], 1 << 30)], 2, -2), ("rows 2^31 - 2", [([2, (1 << 30) - 1, 1], (1 << 30) - 1)], 2, 55),
+]
+
+
+@pytest.mark.parametrize("what,bands,images,want", POOL_GUARDS, ids=[g[0] for g in POOL_GUARDS])
+def test_guards_of_the_pool(what, bands, images, want):
+    lib = S._lib()
+    arr = (_engine.EstimBand * len(bands))(*[_band(ext, rp) for ext, rp in bands])
+    assert lib.mifwt_select_route(0, arr, len(bands), images, 0) == want, what
+    ws = lib.mifwt_select_workspace(0, arr, len(bands), images, 55)
+    assert ws == (0 if want < 0 else images * (2 * 2048 * 4 + 2 * 8)), (what, ws)  # 16 KiB of counters per image, two states
+    # the launching entry refuses the same geometry with the same code (an accepted one is stopped at its missing data pointer)
+    assert lib.mifwt_select_kth(0, arr, len(bands), images, 1, None, 0, 55, None, None, None, 0, None) == (want if want < 0 else -1)
+
+
+def test_the_python_limit_is_the_library_s():
+    lib = S._lib()
+    one = lambda count: lib.mifwt_select_route(0, (_engine.EstimBand * 1)(_band([1, 2, count // 2])), 1, 1, 0)
+    assert S._COUNT_LIMIT == E._COUNT_LIMIT == 1 << 31 and one(S._COUNT_LIMIT - 2) == 55 and one(S._COUNT_LIMIT) == -2
+
+
 def test_k_from_a_fraction():
     table = [(0.07, 100, 7), (0.0, 100, 0), (1.0, 100, 100), (0.5, 3, 2), (0.5, 1, 1), (0.49, 1, 0), (0.05, 1716, 86), (0.005, 100, 1),
              (0.004, 100, 0), (0.999, 1000, 999), (0.9996, 1000, 1000), (1.0, 0, 0), (0.3, 0, 0), (0.15, 10, 2), (0.25, 10, 3)]
@@ -220,3 +250,19 @@ def test_reference_by_hand():
     assert R.kth([a, b], 1, np.array([-3, 9])).tolist() == [np.inf, 0.0]  # clipped
     assert R.kth([a, b], 0, 3).tolist() == 5.0  # one image: 8, 8, 5
     assert R.survivors([a, b], 1, [4.0, 8.0]).tolist() == [2, 2]
+
+
+def test_a_pool_of_2_to_the_31_elements_per_image_is_refused_before_a_device_is_needed():
+    """Past ``_COUNT_LIMIT`` no kernel takes the pool and ``torch.sort``, the composition's selection, takes at most 2^31 - 1 elements:
+    a ``ValueError`` that names the limit, as ``sparse_encode`` raises for its int32 indices (meta tensors: nothing is allocated)."""
+    past, inside = torch.empty((46341, 46341), device="meta"), torch.empty((46340, 46340), device="meta")
+    for fn in (ptwt_amd.keep_threshold, ptwt_amd.sparsify, ptwt_amd.sparse_encode):
+        with pytest.raises(ValueError, match=r"fewer than 2\^31 pooled coefficients per image, got 2147488281"):
+            fn(past, 1000)
+        with pytest.raises(RuntimeError):  # (inside the limit the call goes on to ask for a GPU tensor)
+            fn(inside, 1000)
+    halves = [torch.empty((2, 1), device="meta"), torch.empty((2, 1 << 30), device="meta"), torch.empty((2, 1 << 30), device="meta")]
+    with pytest.raises(ValueError, match=r"fewer than 2\^31 pooled coefficients per image, got 2147483648"):
+        ptwt_amd.keep_threshold(halves, 5)  # two tensors of 2^30 per image pooled
+    with pytest.raises(RuntimeError):
+        ptwt_amd.keep_threshold(halves[:2], 5)
