@@ -679,6 +679,42 @@ int64_t mifwt_estim_moments_plan(int dtype, const mifwt_estim_band* segs, int ns
 int mifwt_estim_thresholds(int dtype, int method, const mifwt_estim_band* segs, int nseg, int64_t images, const double* sigma64,
                            double factor, void* thr, double* thr64, double* moments, void* workspace, size_t workspace_bytes, void* stream);
 
+/* NODE COSTS — the additive cost of every node of a wavelet packet tree, what the Coifman-Wickerhauser best-basis search compares
+ * (csrc/mifwt_cost.hip).  MIFWT_F32 / MIFWT_F64.  A SEGMENT is a band as above whose rows_per_index consecutive rows form one NODE (0:
+ * the whole band is one node); every segment has its own node count, and out[s] receives one float64 per node of segment s.  A level
+ * buffer of a packet tree is one segment, so a whole tree is one call.  With t over the elements of a node, every term evaluated and
+ * accumulated in float64 for both data types:
+ *   MIFWT_COST_SHANNON    -sum t^2 ln t^2            (an element whose square is 0 contributes 0)
+ *   MIFWT_COST_LOGENERGY  sum ln t^2                 (likewise 0)
+ *   MIFWT_COST_NORM       sum |t|^param              (param >= 1 is the caller's; no pow for 1 and 2)
+ *   MIFWT_COST_THRESHOLD  #{|t| > param}             (an exact count)
+ *   MIFWT_COST_SURE       n - #{|t| <= param} + sum min(t^2, param^2)
+ *   mifwt_cost_nodes      kernel id 61, from the node length alone: a node of at most mifwt_cost_short_limit(dtype) elements is summed by
+ *                         a group of 4 / 16 / 64 lanes of a workgroup that takes a run of consecutive nodes, and stored at once; a longer
+ *                         one is cut into chunks of about mifwt_cost_chunk(dtype) elements, a workgroup and one plain store into
+ *                         `workspace` each (8 bytes per unit of mifwt_cost_plan; read only when a segment has long nodes), which a second
+ *                         launch (id 62) adds per node in index order.  No atomics; the plan depends on dtype and shapes only, so the
+ *                         same input gives the same bits.
+ *   mifwt_cost_plan       (host only) the number of units of a table; unit_start, if not NULL, receives nseg + 1 first units.
+ * Nothing is copied to the host and nothing synchronises: the call can be captured.  MIFWT_ERR_BADARG for nseg outside
+ * [1, mifwt_cost_max_segments()], an unknown dtype or functional, a non-unit innermost stride, a rows_per_index that does not divide the
+ * rows, an empty segment or a NULL pointer; MIFWT_ERR_UNSUPPORTED beyond the index range (2^30 elements per row, 2^31 rows, 2^31 elements
+ * per node, 2^31 units); MIFWT_ERR_WORKSPACE for a workspace that is too small.  Nothing is launched then.  Not counted by
+ * mifwt_launch_count. */
+#define MIFWT_KID_COST_NODES 61  /* the costs of the nodes of up to mifwt_cost_max_segments() segments, one launch */
+#define MIFWT_KID_COST_FINISH 62 /* the chunks of every long node added in index order */
+#define MIFWT_COST_SHANNON 0
+#define MIFWT_COST_LOGENERGY 1
+#define MIFWT_COST_NORM 2
+#define MIFWT_COST_THRESHOLD 3
+#define MIFWT_COST_SURE 4
+int mifwt_cost_max_segments(void);
+int64_t mifwt_cost_short_limit(int dtype);
+int64_t mifwt_cost_chunk(int dtype);
+int64_t mifwt_cost_plan(int dtype, const mifwt_estim_band* segs, int nseg, int64_t* unit_start);
+int mifwt_cost_nodes(int dtype, int functional, double param, const mifwt_estim_band* segs, int nseg, double* const* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* SELECTION — the k-th largest magnitude of a coefficient container, pooled per image (csrc/mifwt_select.hip): what keeps the k largest
  * coefficients of every image when mifwt_thresh_fwd reads it as a threshold.  MIFWT_F32 / MIFWT_F64.  `segs` are bands as above that
  * share `images`; per image all their elements form one multiset of n magnitudes (empty bands are skipped; n < 2^31).
@@ -849,7 +885,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *          count, scan and write (mifwt_compact_encode; answered by mifwt_compact_route)
  *   58     scatter / gather between compacted (values, indices) and dense per-tensor storage (mifwt_compact_move)
  *   59 / 60  the tensors of a container and the padding between them into one dense array / blocks of one array into dense tensors,
- *          a box table per launch (mifwt_pack_to_array / mifwt_pack_to_bands; never returned by mifwt_kernel_id) */
+ *          a box table per launch (mifwt_pack_to_array / mifwt_pack_to_bands; never returned by mifwt_kernel_id)
+ *   61 / 62  the additive costs of the nodes of a packet tree, every level a segment of one launch / the chunks of the long nodes added
+ *          in order (mifwt_cost_nodes; never returned by mifwt_kernel_id) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

@@ -18,6 +18,8 @@ of every image over a whole container — an exact radix selection on the device
 ``sparse_encode`` / ``sparse_decode`` compact those ``k`` survivors into ``(values, indices)`` per image and back (``sparse.py``);
 ``coeffs_to_array`` / ``array_to_coeffs`` / ``ravel_coeffs`` / ``unravel_coeffs`` turn a container into ONE tensor in PyWavelets' layouts and
 back, one HIP launch each, and ``wavedecn_shapes`` / ``wavedecn_size`` answer for a shape without a transform (``coeff_array.py``).
+``wentropy`` is the additive cost of a tensor per leading index, and the packet trees choose and rebuild a basis with it —
+``node_costs`` (every node of every level in one HIP launch), ``best_basis``, ``reconstruct_basis`` (``best_basis.py``).
 
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
@@ -49,6 +51,7 @@ from .estimators import estimate_sigma, estimate_thresholds, shrink
 from .sparsify import keep_threshold, sparsify
 from .sparse import SparseCoeffs, sparse_decode, sparse_encode
 from .coeff_array import array_to_coeffs, coeffs_to_array, ravel_coeffs, unravel_coeffs, wavedecn_shapes, wavedecn_size
+from .best_basis import wentropy
 
 __version__ = "0.1.0"
 
@@ -105,4 +108,5 @@ __all__ = [
     "unravel_coeffs",
     "wavedecn_shapes",
     "wavedecn_size",
+    "wentropy",
 ]

@@ -183,6 +183,15 @@ ESTIM_ENTRIES: dict = {
     "mifwt_estim_thresholds": (_c, [_c, _c, _band_p, _c, _i64, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# The node costs of a packet tree (best_basis.py; include/mifwt.h, mifwt_cost_*): bound privately for the same reason.
+COST_ENTRIES: dict = {
+    "mifwt_cost_max_segments": (_c, []),
+    "mifwt_cost_short_limit": (_i64, [_c]),
+    "mifwt_cost_chunk": (_i64, [_c]),
+    "mifwt_cost_plan": (_i64, [_c, _band_p, _c, _i64_p]),
+    "mifwt_cost_nodes": (_c, [_c, _c, ctypes.c_double, _band_p, _c, _vpp, _vp, _sz, _vp]),
+}
+
 # The pooled selection (sparsify.py; include/mifwt.h, mifwt_select_*): bound privately for the same reason.
 SELECT_ENTRIES: dict = {
     "mifwt_select_max_segments": (_c, []),

@@ -32,6 +32,9 @@ out one sample long, not the root.  Differentiable w.r.t. the data; a learnable 
 
 ``mode="smooth"`` / ``"antisymmetric"`` / ``"antireflect"`` are padded modes: the level buffers, keys and ``reconstruct`` of the padded
 modes, with ``_ext.fwd`` (kernel ids 42 / 44) as the level call; the same refusals as ``"periodization"``.
+
+``node_costs`` / ``best_basis`` / ``reconstruct_basis`` — the Coifman-Wickerhauser best-basis search and the reconstruction from a
+non-uniform basis — are bound into ``_PacketTree`` by ``best_basis.py``; the three reconstruct loops below take the per-level hook it uses.
 """
 from __future__ import annotations
 
@@ -275,12 +278,17 @@ class _PacketTree(collections.UserDict):
             return self._reconstruct_boundary()
         if self._periodized:
             return self._reconstruct_periodized()
+        return self._reconstruct_padded()
+
+    def _reconstruct_padded(self, top: Optional[int] = None, override=None):
+        """``reconstruct`` in the padded modes, from the nodes of level ``top`` (``maxlevel``).  ``override(level, buf)``, when given,
+        returns the buffer that stands for the rebuilt ``level`` from then on (``reconstruct_basis``, best_basis.py)."""
         _, _, rec_lo, rec_hi = host_taps(self.wavelet)
         tap_t = _fwt._tap_tensors(self.wavelet)
         flen = len(rec_lo)
         nb = len(self._bands)
         nd = self._ndim
-        for level in reversed(range(self.maxlevel)):
+        for level in reversed(range(self.maxlevel if top is None else top)):
             for node in self._keys_of_level(level):
                 for child in self._bands:
                     if node + child not in self.data:
@@ -302,6 +310,8 @@ class _PacketTree(collections.UserDict):
             else:
                 rec = _engine.ENGINE.synthesis(approx, details, rec_lo, rec_hi, out_ext)
             buf = rec.reshape(children.shape[0], *([nb] * level), *rec.shape[1:])
+            if override is not None:
+                buf = override(level, buf)
             while len(self._levels) <= level:
                 self._levels.append(None)
             self._levels[level] = buf
@@ -321,16 +331,17 @@ class _PacketTree(collections.UserDict):
         key = self._keys_of_level(level)[0]
         return tuple(self._layout.fold(self.data[key]).shape[1:]) if key in self.data else None
 
-    def _reconstruct_boundary(self):
+    def _reconstruct_boundary(self, top: Optional[int] = None, override=None):
         """``reconstruct`` with the transposed boundary-wavelet level maps; a node that comes out one sample long is cropped to the
-        extents it had, the root is not.  1-D, no gradient wanted: runs of levels that double exactly go through one subtree launch."""
+        extents it had, the root is not.  1-D, no gradient wanted: runs of levels that double exactly go through one subtree launch.
+        ``top`` / ``override``: as in ``_reconstruct_padded``; with a hook every level is a launch of its own."""
         bank, nb, nd = self._banks[1], len(self._bands), self._ndim
-        level = self.maxlevel
+        level = self.maxlevel if top is None else top
         while level > 0:
             self._require_children(level - 1)
             children = self._level_buffer(level)  # [B, nb^level.., M..]
             k = 1
-            if nd == 1 and not (torch.is_grad_enabled() and children.requires_grad):
+            if nd == 1 and override is None and not (torch.is_grad_enabled() and children.requires_grad):
                 # levels above that are exactly twice as long as the one below them: the levels the analysis finds even.  (A root of odd
                 # length comes back one sample longer, uncropped, from the per-level launch.)
                 m, up = int(children.shape[-1]), 0
@@ -356,15 +367,16 @@ class _PacketTree(collections.UserDict):
                             assert out_ext[a] == target[a] + 1, "padding error, please open an issue on github"
                             out_ext[a] = int(target[a])
                 rec = _boundary_transposed([flat[:, s] for s in range(nb)], bank, tuple(out_ext))
-                self._replace_level(level - 1, rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:]))
+                buf = rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:])
+                self._replace_level(level - 1, buf if override is None else override(level - 1, buf))
             level -= k
         return self
 
-    def _reconstruct_periodized(self):
+    def _reconstruct_periodized(self, top: Optional[int] = None, override=None):
         """``reconstruct`` with one periodized synthesis launch per level; a node that comes out one sample long is cropped to the
-        extents it had, the root is not."""
+        extents it had, the root is not.  ``top`` / ``override``: as in ``_reconstruct_padded``."""
         nb, nd = len(self._bands), self._ndim
-        for level in range(self.maxlevel, 0, -1):
+        for level in range(self.maxlevel if top is None else top, 0, -1):
             self._require_children(level - 1)
             children = self._level_buffer(level)  # [B, nb^level.., M..]
             flat = children.reshape(-1, nb, *children.shape[1 + level:])
@@ -376,7 +388,8 @@ class _PacketTree(collections.UserDict):
             if target is not None:
                 out_ext = [n - _fwt._adjust_trim(n, int(target[a])) for a, n in enumerate(out_ext)]
             rec = _per.inv([flat[:, s] for s in range(nb)], rec_lo, rec_hi, out_ext)
-            self._replace_level(level - 1, rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:]))
+            buf = rec.reshape(children.shape[0], *([nb] * (level - 1)), *rec.shape[1:])
+            self._replace_level(level - 1, buf if override is None else override(level - 1, buf))
         return self
 
     def _replace_level(self, level: int, buf: torch.Tensor) -> None:
