@@ -715,6 +715,53 @@ int64_t mifwt_cost_plan(int dtype, const mifwt_estim_band* segs, int nseg, int64
 int mifwt_cost_nodes(int dtype, int functional, double param, const mifwt_estim_band* segs, int nseg, double* const* out, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* MULTIRESOLUTION ANALYSIS — every component of a decomposition back in the signal domain, all of them in one launch
+ * (csrc/mifwt_mra.hip).  MIFWT_F32 / MIFWT_F64, even L <= 20, unit innermost strides.  A COMPONENT is the synthesis of ONE band with
+ * every other band absent: `depth` one-input stages, the first with rec_hi (`detail` != 0) or rec_lo, the others with rec_lo.  Band b
+ * is [rows, len] at `x` with `row_stride` elements between rows (any view: nothing is copied), and its component is written to
+ * out + index * out_comp_stride + row * out_row_stride, n samples per row.  A workgroup takes one (tile of mifwt_mra_tile() outputs,
+ * band, row), stages the window of the band its tile depends on into LDS through the boundary's index map, runs the stages between two
+ * LDS buffers and writes its tile once.  float32 data is summed in float32 FMAs, float64 in float64; no atomics, nothing is read
+ * back: the calls can be captured.
+ *   mifwt_mra_swt   kernel id 63, stationary (mifwt_swt_inv with one band absent; len = n).  The stage of level l, l = depth .. 1, has
+ *                   dilation D = 2^(l-1):   y[n] = 0.5 sum_i r[i] c[(n + D (L/2 - 1 - i)) mod N]
+ *                   so that  D_j = U_1 .. U_{j-1} G_j W_j  and  S_n = U_1 .. U_n V_n  (U: rec_lo, G: rec_hi).  The window a tile needs at
+ *                   depth j grows by (2^j - 1) L/2 on the left and (2^j - 1)(L/2 - 1) on the right; it wraps as often as N asks.
+ *   mifwt_mra_dwt   kernel id 64, decimated.  level_len[l], l = 0 .. nlevels, is the length of a row at level l (0: the signal, n); a
+ *                   band of depth j has level_len[j] samples.  A stage takes level l to l - 1; even / odd outputs use the even / odd
+ *                   taps.  Padded (`circular` 0; the synthesis does not depend on the padding mode):
+ *                       y[n] = sum_k c[k] r[n + L - 2 - 2k],  n in [0, level_len[l-1]),  level_len[l-1] = 2 level_len[l] - L + 2 or one less
+ *                   periodized (`circular` != 0):
+ *                       y[(2k + t - L/2 + 1) mod 2 level_len[l]] += c[k] r[t],  level_len[l-1] = 2 level_len[l] or one less
+ *                   A level shorter than its full synthesis loses its LAST sample.
+ *   mifwt_mra_max_depth  (host only, needs no device) the deepest component the launch of `transform` takes: for MIFWT_MRA_SWT the largest
+ *                   j with (2^j - 1)(L - 1) <= 2048 — two LDS buffers of 4096 elements under a 2048-sample tile: db4 to 8, db10 to 6 —,
+ *                   for MIFWT_MRA_DWT 32; 0 for 16-bit storage and L > 20.
+ * MIFWT_ERR_BADARG for a NULL pointer, an odd L, nbands < 1, a depth < 1, level lengths that are not one decomposition's;
+ * MIFWT_ERR_UNSUPPORTED for L > 20, 16-bit storage, more than mifwt_mra_max_bands() bands, a band deeper than mifwt_mra_max_depth, rows
+ * or n above 2^30, or (periodized levels of very few samples) a window that outgrows the LDS buffers.  Nothing is launched then.  Not
+ * counted by mifwt_launch_count. */
+#define MIFWT_KID_MRA_SWT 63 /* all components of a stationary decomposition, one launch */
+#define MIFWT_KID_MRA_DWT 64 /* all components of a decimated decomposition (padded or periodized), one launch */
+#define MIFWT_MRA_SWT 0
+#define MIFWT_MRA_DWT 1
+typedef struct mifwt_mra_band {
+  const void* x;
+  int64_t row_stride; /* elements */
+  int32_t index;      /* which component of `out` */
+  int32_t depth;      /* stages */
+  int32_t detail;     /* first stage: 0 rec_lo, else rec_hi */
+  int32_t reserved;
+} mifwt_mra_band;
+int64_t mifwt_mra_tile(void);
+int mifwt_mra_max_bands(void);
+int mifwt_mra_max_depth(int dtype, int filt_len, int transform);
+int mifwt_mra_swt(int dtype, int filt_len, int64_t rows, int64_t n, const mifwt_mra_band* bands, int nbands, void* out,
+                  int64_t out_comp_stride, int64_t out_row_stride, const double* rec_lo, const double* rec_hi, void* stream);
+int mifwt_mra_dwt(int dtype, int filt_len, int circular, int64_t rows, const int64_t* level_len, int nlevels, const mifwt_mra_band* bands,
+                  int nbands, void* out, int64_t out_comp_stride, int64_t out_row_stride, const double* rec_lo, const double* rec_hi,
+                  void* stream);
+
 /* SELECTION — the k-th largest magnitude of a coefficient container, pooled per image (csrc/mifwt_select.hip): what keeps the k largest
  * coefficients of every image when mifwt_thresh_fwd reads it as a threshold.  MIFWT_F32 / MIFWT_F64.  `segs` are bands as above that
  * share `images`; per image all their elements form one multiset of n magnitudes (empty bands are skipped; n < 2^31).
@@ -887,7 +934,9 @@ size_t mifwt_workspace_bytes(const mifwt_level_desc* desc, int direction);
  *   59 / 60  the tensors of a container and the padding between them into one dense array / blocks of one array into dense tensors,
  *          a box table per launch (mifwt_pack_to_array / mifwt_pack_to_bands; never returned by mifwt_kernel_id)
  *   61 / 62  the additive costs of the nodes of a packet tree, every level a segment of one launch / the chunks of the long nodes added
- *          in order (mifwt_cost_nodes; never returned by mifwt_kernel_id) */
+ *          in order (mifwt_cost_nodes; never returned by mifwt_kernel_id)
+ *   63 / 64  every component of a multiresolution analysis in one launch: stationary / decimated (mifwt_mra_swt / mifwt_mra_dwt;
+ *          never returned by mifwt_kernel_id) */
 int mifwt_kernel_id(const mifwt_level_desc* desc, int direction);
 
 /* Library-wide diagnostic switches (process-global, meant for tests and A/B measurements).

@@ -20,6 +20,8 @@ of every image over a whole container — an exact radix selection on the device
 back, one HIP launch each, and ``wavedecn_shapes`` / ``wavedecn_size`` answer for a shape without a transform (``coeff_array.py``).
 ``wentropy`` is the additive cost of a tensor per leading index, and the packet trees choose and rebuild a basis with it —
 ``node_costs`` (every node of every level in one HIP launch), ``best_basis``, ``reconstruct_basis`` (``best_basis.py``).
+``mra`` / ``imra`` split a signal into the ``level + 1`` signals of its own shape that its bands reconstruct one at a time (``pywt.mra``),
+over ``swt`` or ``wavedec``: all components in one HIP launch (``mra.py``).
 
     import ptwt_amd as ptwt
     coeffs = ptwt.wavedec2(x.cuda(), "db4", level=3)
@@ -52,6 +54,7 @@ from .sparsify import keep_threshold, sparsify
 from .sparse import SparseCoeffs, sparse_decode, sparse_encode
 from .coeff_array import array_to_coeffs, coeffs_to_array, ravel_coeffs, unravel_coeffs, wavedecn_shapes, wavedecn_size
 from .best_basis import wentropy
+from .mra import imra, mra
 
 __version__ = "0.1.0"
 
@@ -109,4 +112,6 @@ __all__ = [
     "wavedecn_shapes",
     "wavedecn_size",
     "wentropy",
+    "mra",
+    "imra",
 ]

@@ -192,6 +192,23 @@ COST_ENTRIES: dict = {
     "mifwt_cost_nodes": (_c, [_c, _c, ctypes.c_double, _band_p, _c, _vpp, _vp, _sz, _vp]),
 }
 
+# The multiresolution analysis (mra.py; include/mifwt.h, mifwt_mra_*): bound privately for the same reason.
+class MraBand(ctypes.Structure):
+    """``mifwt_mra_band``: one band of a decomposition and the component it becomes."""
+
+    _fields_ = [("x", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("index", ctypes.c_int32), ("depth", ctypes.c_int32),
+                ("detail", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_mra_p = ctypes.POINTER(MraBand)
+MRA_ENTRIES: dict = {
+    "mifwt_mra_tile": (_i64, []),
+    "mifwt_mra_max_bands": (_c, []),
+    "mifwt_mra_max_depth": (_c, [_c, _c, _c]),
+    "mifwt_mra_swt": (_c, [_c, _c, _i64, _i64, _mra_p, _c, _vp, _i64, _i64, _dbl_p, _dbl_p, _vp]),
+    "mifwt_mra_dwt": (_c, [_c, _c, _c, _i64, _i64_p, _c, _mra_p, _c, _vp, _i64, _i64, _dbl_p, _dbl_p, _vp]),
+}
+
 # The pooled selection (sparsify.py; include/mifwt.h, mifwt_select_*): bound privately for the same reason.
 SELECT_ENTRIES: dict = {
     "mifwt_select_max_segments": (_c, []),
